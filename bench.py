@@ -11,12 +11,19 @@ N > 1 (launched by torch.distributed.run, one rank per GPU): STRONG scaling of t
 sharded by the reference's ByApplication rule (IndexingData.h:117-146), every rank evaluates its shard into its own
 HBM buffer, and the per-shard FX / AGX / KKT blocks are gathered to rank 0 with ONE device-to-device RCCL gather
 (xGMI) inside the timed region, each step -- the exchange a host KKT system on rank 0 needs every PSIOPT iteration.
-`value` counts the whole phase's segments per second WITH the exchange; the line also carries the rate without it,
-the exchange time alone and every rank's kernel time.  Workload `multispacecraft_8x1250` (BASELINE.json configs[3])
+`value` counts the whole phase's segments per second WITH the exchange; with --full the line also carries the rate without
+it, the exchange time alone and every rank's kernel time.  Workload `multispacecraft_8x1250` (BASELINE.json configs[3])
 deals whole phases to the ranks instead.
 
-Prints ONE JSON line (rank 0) carrying `roofline` (HBM, algorithmic bytes / HIP-event kernel time) and, at N=1,
-`cpu_baseline` (the oracle's multi-threaded C++ restatement of the reference's evalKKT on the host cores).
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times the --steps steps and reports `value` and `ms_per_step`
+(the host clock around the timed steps, ending in a device synchronisation) and nothing else.  `--full` adds everything else
+the benchmark measures, each in runs of its own: `roofline` (HBM, algorithmic bytes / HIP-event kernel
+time), the secondary evaluation kinds, the exchange alone (N > 1), the host-visible rates and, at N=1, `cpu_baseline` (the
+oracle's multi-threaded C++ restatement of the reference's evalKKT on the host cores; `--no-cpu-baseline` leaves it out).
+
+`--dump-outputs DIR` writes what the timed path computed in its last step -- the per-segment blocks a caller receives --
+as DIR/fx.npy, DIR/agx.npy and DIR/kkt.npy (float64; see dump_outputs).  The inputs are seeded: the same arguments give the
+same inputs in every run.
 """
 from __future__ import annotations
 
@@ -51,11 +58,36 @@ WORKLOADS = {
 MULTI_PHASE = {"multispacecraft_8x1250": 8}
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec (6.3 TB/s achievable)
 FP64_PEAK_GFLOPS = 78600.0  # MI355X FP64 vector = FP64 matrix: 16 FMA lanes per cycle and SIMD (half the 157.3 TFLOP/s FP32 vector rate of MI355X_MICROARCH.md)
+DUMP_BYTES = 60_000_000  # --dump-outputs: at most this much data in all (the blocks of the default workload hold 84 MB)
+DUMP_SEED = 2024
 
 
 def algorithmic_bytes_per_segment(IR, OR):
     """reads z, lam; writes fx, adjgrad, H lower triangle, J."""
     return 8 * ((IR + OR) + (OR + IR + IR * (IR + 1) // 2 + OR * IR))
+
+
+def dump_outputs(directory, fx, agx, kkt, kkt_to_reference):
+    """Write the blocks of the last step as float64 .npy files: fx [n, OR] (defect values), agx [n, IR] (adjoint gradient)
+    and kkt [n, NKKT] (Jacobian and adjoint-Hessian entries in the reference's order, the padding of the handle's layout
+    dropped).  fx / agx / kkt: device tensors [nseg, ...] in the handle's layout.  Every segment when the three fit in
+    DUMP_BYTES; otherwise the same seeded sample of segments, ascending, from each -- it depends on the workload alone, so two
+    builds dump the same rows."""
+    import numpy as np
+    import torch
+
+    nseg, OR, IR = fx.shape[0], fx.shape[1], agx.shape[1]
+    row_bytes = 8 * (OR + IR + IR * (IR + 1) // 2 + OR * IR)
+    if nseg * row_bytes <= DUMP_BYTES:
+        rows = np.arange(nseg)
+    else:
+        rows = np.sort(np.random.default_rng(DUMP_SEED).choice(nseg, DUMP_BYTES // row_bytes, replace=False))
+    idx = torch.from_numpy(rows).to(fx.device)
+    os.makedirs(directory, exist_ok=True)
+    for name, t in (("fx", fx), ("agx", agx), ("kkt", kkt)):
+        a = t.index_select(0, idx).cpu().numpy().astype(np.float64)
+        np.save(os.path.join(directory, f"{name}.npy"), np.ascontiguousarray(kkt_to_reference(a)) if name == "kkt" else a)
+    print(f"[bench] outputs of the last step: {rows.size} of {nseg} segments -> {directory}", file=sys.stderr)
 
 
 def physical_cores() -> int:
@@ -158,11 +190,18 @@ def main():
     ap.add_argument("--steps", type=int, default=1000)
     ap.add_argument("--warmup", type=int, default=50)
     ap.add_argument("--workload", default="reentry_lgl7_10k", choices=sorted(WORKLOADS))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the roofline, the secondary kinds, the exchange alone, the host-visible rates and "
+                         "(N = 1) the CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the blocks the last timed step computed as DIR/<name>.npy (float64)")
     ap.add_argument("--inprocess-shards", type=int, default=0,
                     help="N >= 1: also time the constraint as N device handles in THIS process (the C ABI's asset_hip_defect_create_sharded, "
                          "shard k on device k mod the visible devices): host-visible rates of the blocks and of the assembled values")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -325,7 +364,8 @@ def main():
     # Kernel-only duration of this rank's share on the handle's own stream, HIP events around the launches -- measured
     # FIRST and until it settles: the part clocks up under load (the same kernel: 49.8 us over the first 100 launches after
     # an idle second, 45.2 after 300, 42.6 after 900), so the rounds below are repeated until two agree within 1 %.  The
-    # timed region of the contract follows immediately, on a device that is already at its working clocks.
+    # timed region of the contract follows immediately, on a device that is already at its working clocks -- in a plain run
+    # as well: there the rounds are the first part of the warm-up and their figure is not reported.
     ms_kernel, kernel_rounds, ms_con, ms_rhs, ms_soe, ms_aug, ms_soe_keep, ms_aug_keep = 0.0, [], 0.0, 0.0, 0.0, 0.0, 0.0, 0.0
     if evs:
         e0 = evs[0]
@@ -340,20 +380,29 @@ def main():
             if len(kernel_rounds) >= 2 and abs(kernel_rounds[-1] - kernel_rounds[-2]) <= 0.01 * kernel_rounds[-1]:
                 break
         ms_kernel = kernel_rounds[-1]
-        # secondary number: the value-only kind, evalOCC / CON -- what a line search calls
-        ms_con = e0.time_device(CON, X, None, kfx, None, None, warmup=5, iters=iters)
-        ms_rhs = e0.time_device(CON_ADJGRAD, X, L, kfx, kagx, None, warmup=5, iters=iters)   # evalRHS: value + J^T lam
-        ms_soe = e0.time_device(JAC, X, None, kfx, None, kkkt, warmup=5, iters=iters)         # evalSOE: value + Jacobian blocks
-        ms_aug = e0.time_device(JAC_ADJGRAD, X, L, kfx, kagx, kkkt, warmup=5, iters=iters)    # evalAUG
-        # the same two with the Hessian slots of the blocks left untouched (KKTFillJac never reads them)
-        ms_soe_keep = e0.time_device(JAC | KEEP_HESSIAN_SLOTS, X, None, kfx, None, kkkt, warmup=5, iters=iters)
-        ms_aug_keep = e0.time_device(JAC_ADJGRAD | KEEP_HESSIAN_SLOTS, X, L, kfx, kagx, kkkt, warmup=5, iters=iters)
+        if a.full:
+            # secondary number: the value-only kind, evalOCC / CON -- what a line search calls
+            ms_con = e0.time_device(CON, X, None, kfx, None, None, warmup=5, iters=iters)
+            ms_rhs = e0.time_device(CON_ADJGRAD, X, L, kfx, kagx, None, warmup=5, iters=iters)   # evalRHS: value + J^T lam
+            ms_soe = e0.time_device(JAC, X, None, kfx, None, kkkt, warmup=5, iters=iters)         # evalSOE: value + Jacobian blocks
+            ms_aug = e0.time_device(JAC_ADJGRAD, X, L, kfx, kagx, kkkt, warmup=5, iters=iters)    # evalAUG
+            # the same two with the Hessian slots of the blocks left untouched (KKTFillJac never reads them)
+            ms_soe_keep = e0.time_device(JAC | KEEP_HESSIAN_SLOTS, X, None, kfx, None, kkkt, warmup=5, iters=iters)
+            ms_aug_keep = e0.time_device(JAC_ADJGRAD | KEEP_HESSIAN_SLOTS, X, L, kfx, kagx, kkkt, warmup=5, iters=iters)
         del kfx, kagx, kkkt
 
     dt = timed(step, a.steps, a.warmup)                       # THE measurement: K steps, exchange included when N > 1
     ms_timed_region = last_event_ms[0] / a.steps              # average launch-to-launch duration over the timed region
+    if a.dump_outputs and rank == 0:                          # (before anything else is evaluated into the same buffers)
+        if exchange is None:
+            dump_outputs(a.dump_outputs, fx.view(nseg, OR), agx.view(nseg, IR), kkt.view(nseg, KSTRIDE), ev.kkt_to_reference)
+        else:
+            blocks = sh.blocks_on_root()
+            if nphases > 1:
+                blocks = tuple(torch.cat([b[k] for b in blocks]) for k in range(3))
+            dump_outputs(a.dump_outputs, *blocks, sh.kkt_to_reference)
     extra = {}
-    if exchange is not None and use_dist:
+    if a.full and exchange is not None and use_dist:
         k2 = max(10, min(a.steps, 200))
         extra["ms_per_step_without_exchange"] = timed(evaluate, k2, 5) / k2 * 1e3
         extra["value_without_exchange"] = total_segments / (extra["ms_per_step_without_exchange"] * 1e-3)
@@ -364,7 +413,7 @@ def main():
     # rank copies its shard over its own PCIe link into its range of one page-locked host buffer all ranks map
     # (asset_asrl_amd/distributed.py: HostSharedBlocks); the step ends at a barrier.  One GPU: one link.
     host_visible = None
-    if nphases == 1 and nseg * (OR + IR + NKKT) * 8 <= 4 << 30:
+    if a.full and nphases == 1 and nseg * (OR + IR + NKKT) * 8 <= 4 << 30:
         k3 = max(5, min(a.steps, 50))
         ok = 1
         if use_dist:
@@ -484,7 +533,7 @@ def main():
     ms_roof = ms_timed_region if (world == 1 and exchange is None) else ms_kernel
     achieved = local_segments * bseg / (ms_roof * 1e-3) / 1e9 if ms_roof > 0 else 0.0
     per_rank_ms, per_rank_segments = [ms_kernel], [local_segments]
-    if dist is not None:
+    if a.full and dist is not None:
         t = torch.tensor([ms_kernel, float(local_segments)], dtype=torch.float64, device=dev)
         allk = [torch.zeros_like(t) for _ in range(world)]
         dist.all_gather(allk, t)
@@ -497,7 +546,7 @@ def main():
     # sparse form (asset_asrl_amd/flopcount.py) against the FP64 vector peak, the arithmetic intensity against the ridge, and -- from the
     # committed counter profile -- the flops the kernels ISSUE if every vector instruction were a 64-lane FMA (an upper bound)
     fp64 = None
-    if mode != "Trapezoidal":
+    if a.full and mode != "Trapezoidal":
         from asset_asrl_amd import synth
         from asset_asrl_amd.flopcount import sparse_useful_flops
         from asset_asrl_amd.ode import ODE_LIBRARY
@@ -512,7 +561,7 @@ def main():
 
     traffic, traffic_src = None, None
     prof = next((q for q in (os.path.join(ROOT, "profiles", f"r{r}_{a.workload}_pmc.json") for r in (6, 5, 4, 3, 2)) if os.path.exists(q)), "")
-    if world == 1 and prof:   # NOT measured by this run: HBM bytes per evaluation from the committed rocprofv3 --pmc passes
+    if a.full and world == 1 and prof:   # NOT measured by this run: HBM bytes per evaluation from the committed rocprofv3 --pmc passes
         try:
             pj = json.load(open(prof))
             traffic = pj["hbm"]["bytes_per_launch"]
@@ -565,29 +614,32 @@ def main():
                                          "xGMI inside the evaluation; `value` adds the device-to-device gather of all blocks into rank 0, which a "
                                          "host-resident solver does not need (`host_visible_assembled`: every rank pushes its assembled values "
                                          "over its own PCIe link)")},
-            "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_src,
-                         "kernel": ("lgl_defect_kernel (ODE stage) + lgl_rows_kernel (dense stage by output rows; LGL3: lgl_wide_dense_kernel)" if IR >= 64 else
-                                    "lgl_resident_kernel (one launch, ODE results resident in LDS; dense part as matrix-instruction tiles, or by "
-                                    "output rows with DPP-broadcast operands for the shapes the tiles would pad: defect_rowdpp.h) for the narrow LGL shapes; otherwise "
-                                    "lgl_defect_kernel (fused launch, or ODE-stage + dense-stage launches; ODE stage in units for heavy ODEs)")
-                                   + "; rank 0's share, all launches of one evaluation timed",
-                         "launch_ms": ms_roof, "launch_ms_source": ("HIP events around the K timed steps / K" if ms_roof is ms_timed_region
-                                                                     else "settled HIP-event rounds (the step also holds the exchange)"),
-                         "kernel_ms": ms_kernel, "kernel_ms_rounds": kernel_rounds, "segments_in_kernel": local_segments,
-                         "algorithmic_bytes_per_segment": bseg, "fp64": fp64},
-            "per_rank_kernel_ms": per_rank_ms, "per_rank_segments": per_rank_segments, "per_rank_roofline_frac": per_rank_frac,
-            "secondary": {"evalOCC (CON: defect values only), rank 0's share, kernel": {
-                "ms": ms_con, "segments_per_s": local_segments / (ms_con * 1e-3) if ms_con > 0 else 0.0,
-                "algorithmic_bytes_per_segment": 8 * (IR + OR) + 8 * OR},
-                "evalRHS (CON_ADJGRAD: values + adjoint gradient, no Jacobian formed), rank 0's share, kernel": {
-                "ms": ms_rhs, "segments_per_s": local_segments / (ms_rhs * 1e-3) if ms_rhs > 0 else 0.0,
-                "algorithmic_bytes_per_segment": 8 * (IR + OR) + 8 * (OR + IR)},
-                "evalSOE (JAC: values + Jacobian blocks, Hessian slots zero), kernel ms": ms_soe,
-                "evalAUG (JAC_ADJGRAD), kernel ms": ms_aug,
-                "evalSOE with the Hessian slots left untouched (JAC | KEEP_HESSIAN_SLOTS), kernel ms": ms_soe_keep,
-                "evalAUG with the Hessian slots left untouched (JAC_ADJGRAD | KEEP_HESSIAN_SLOTS), kernel ms": ms_aug_keep},
         }
+        if a.full:
+            out.update({
+                "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                             "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_src,
+                             "kernel": ("lgl_defect_kernel (ODE stage) + lgl_rows_kernel (dense stage by output rows; LGL3: lgl_wide_dense_kernel)" if IR >= 64 else
+                                        "lgl_resident_kernel (one launch, ODE results resident in LDS; dense part as matrix-instruction tiles, or by "
+                                        "output rows with DPP-broadcast operands for the shapes the tiles would pad: defect_rowdpp.h) for the narrow LGL shapes; otherwise "
+                                        "lgl_defect_kernel (fused launch, or ODE-stage + dense-stage launches; ODE stage in units for heavy ODEs)")
+                                       + "; rank 0's share, all launches of one evaluation timed",
+                             "launch_ms": ms_roof, "launch_ms_source": ("HIP events around the K timed steps / K" if ms_roof is ms_timed_region
+                                                                         else "settled HIP-event rounds (the step also holds the exchange)"),
+                             "kernel_ms": ms_kernel, "kernel_ms_rounds": kernel_rounds, "segments_in_kernel": local_segments,
+                             "algorithmic_bytes_per_segment": bseg, "fp64": fp64},
+                "per_rank_kernel_ms": per_rank_ms, "per_rank_segments": per_rank_segments, "per_rank_roofline_frac": per_rank_frac,
+                "secondary": {"evalOCC (CON: defect values only), rank 0's share, kernel": {
+                    "ms": ms_con, "segments_per_s": local_segments / (ms_con * 1e-3) if ms_con > 0 else 0.0,
+                    "algorithmic_bytes_per_segment": 8 * (IR + OR) + 8 * OR},
+                    "evalRHS (CON_ADJGRAD: values + adjoint gradient, no Jacobian formed), rank 0's share, kernel": {
+                    "ms": ms_rhs, "segments_per_s": local_segments / (ms_rhs * 1e-3) if ms_rhs > 0 else 0.0,
+                    "algorithmic_bytes_per_segment": 8 * (IR + OR) + 8 * (OR + IR)},
+                    "evalSOE (JAC: values + Jacobian blocks, Hessian slots zero), kernel ms": ms_soe,
+                    "evalAUG (JAC_ADJGRAD), kernel ms": ms_aug,
+                    "evalSOE with the Hessian slots left untouched (JAC | KEEP_HESSIAN_SLOTS), kernel ms": ms_soe_keep,
+                    "evalAUG with the Hessian slots left untouched (JAC_ADJGRAD | KEEP_HESSIAN_SLOTS), kernel ms": ms_aug_keep},
+            })
         out.update(extra)
         if host_visible is not None:
             out["host_visible"] = host_visible
@@ -595,7 +647,7 @@ def main():
             out["host_visible_assembled"] = host_visible_assembled
         if inprocess is not None:
             out["inprocess_shards"] = inprocess
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full and world == 1 and not a.no_cpu_baseline:
             # bounded sample: the oracle's CSR scatter needs 12 B per KKT slot on the host -- cap it at 2e8 slots
             cap = max(1, int(2e8) // NKKT)
             wc = w if nseg <= cap else Workload(ode, mode, cap, blocked)

@@ -83,7 +83,7 @@ def test_sharded_device_path_with_rccl_gather_matches_the_oracle(oracle):
 @pytest.mark.gpu
 def test_bench_runs_the_exchange_path_with_one_rank():
     env = dict(os.environ, ASSET_BENCH_FORCE_DIST="1")
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "5", "--warmup", "2", "--no-cpu-baseline"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "5", "--warmup", "2", "--full", "--no-cpu-baseline"],
                        capture_output=True, text=True, timeout=900, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     assert r.stdout.strip().splitlines()[-1].startswith("{"), r.stdout[-500:]      # the JSON line is the last line

@@ -11,10 +11,10 @@ for wl in $wls; do
   for n in 1 2 4 8; do
     [ $n -gt $ngpu ] && continue
     if [ $n -eq 1 ]; then
-      python3 $R/bench.py --workload $wl --no-cpu-baseline 2>/dev/null | tail -1 >> $out
+      python3 $R/bench.py --workload $wl --full --no-cpu-baseline 2>/dev/null | tail -1 >> $out
     else
       python3 -m torch.distributed.run --nnodes=1 --nproc-per-node $n --master-addr 127.0.0.1 --master-port $((29500 + n)) \
-        $R/bench.py --gpus $n --workload $wl --no-cpu-baseline 2>/dev/null | tail -1 >> $out
+        $R/bench.py --gpus $n --workload $wl --full --no-cpu-baseline 2>/dev/null | tail -1 >> $out
     fi
   done
 done
