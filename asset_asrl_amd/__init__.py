@@ -1,0 +1,2 @@
+"""ASSET optimal-control transcriptions on AMD Instinct GPUs (HIP)."""
+from .interp import LGLInterpTable  # noqa: F401

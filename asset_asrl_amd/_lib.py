@@ -64,6 +64,12 @@ SYMBOLS = {
     "asset_hip_sharded_set_kkt_map": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_longlong]),
     "asset_hip_sharded_eval_assembled": (C.c_int, [C.c_void_p, C.c_int, _dp, _dp, _dp, _dp, _dp]),
     "asset_hip_mesh_error_deboor": (C.c_int, [C.c_char_p, C.c_int, C.c_int, _dp, C.c_int, _dp, _dp, _dp, _dp, _dp, C.c_int]),
+    "asset_hip_traj_table_create": (C.c_int, [C.c_char_p, C.c_int, C.c_int, _dp, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
+    "asset_hip_traj_table_interp": (C.c_int, [C.c_void_p, _dp, C.c_longlong, C.c_int, _dp, _dp, C.POINTER(C.c_longlong)]),
+    "asset_hip_traj_table_interp_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_longlong, C.c_int, C.c_void_p, C.c_void_p,
+                                                    C.c_void_p, C.c_void_p]),
+    "asset_hip_traj_table_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), _dp, _dp]),
+    "asset_hip_traj_table_destroy": (None, [C.c_void_p]),
     "asset_hip_host_register": (C.c_int, [C.c_void_p, C.c_size_t]),
     "asset_hip_host_unregister": (C.c_int, [C.c_void_p]),
     "asset_hip_num_odes": (C.c_int, []),

@@ -4,6 +4,7 @@
 
 #include <memory>
 
+#include <cmath>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -849,6 +850,143 @@ int asset_hip_mesh_error_deboor(const char* ode, int mode, int blocked, const do
   if (dist_max && (e = hipMemcpy(dist_max, a.dist_max, (nb + 1) * sizeof(double), hipMemcpyDeviceToHost)) != hipSuccess)
     return done(hipfail(e, "hipMemcpy(dist_max)"));
   return done(0);
+}
+
+// ---------------------------------------------------------------------------------------------- trajectory table
+
+struct asset_hip_traj_table {
+  const asset_hip::KernelEntry* ke = nullptr;
+  int nb = 0, nnodes = 0, N = 0, n = 0, device = 0, cus = 256;
+  double t0 = 0.0, tf = 0.0;
+  double* d_buf = nullptr;     // traj | xdot | tb, resident
+  asset_hip::InterpArgs a{};
+  // staging of the host-pointer entry point (grown on demand): times | out | dout, and the counter
+  double* d_stage = nullptr;
+  long long cap_q = 0;
+  unsigned long long* d_count = nullptr;
+  hipStream_t stream = nullptr;
+};
+
+int asset_hip_traj_table_create(const char* ode, int mode, int blocked, const double* traj, int nnodes, int device,
+                                asset_hip_traj_table_t* out) {
+  if (!ode || !traj || !out) return fail(ASSET_HIP_EINVAL, "null argument");
+  *out = nullptr;
+  const asset_hip::KernelEntry* ke = find_entry(ode, mode, blocked);
+  if (!ke) return fail(ASSET_HIP_ENOODE, std::string("no device code compiled for ode='") + ode + "' in this mode");
+  if (ke->table->meta[asset_hip::MF_KIND] != 1 || !asset_hip::entry_has_interp(ke))
+    return fail(ASSET_HIP_EINVAL, "this entry has no trajectory-table kernels (it is not a transcription of an ODE)");
+  const int K = asset_hip::interp_basis(mode).cs - 1, n = ke->xv, N = ke->xv + 1 + ke->uv + ke->pv;
+  if (nnodes < 2 || (nnodes - 1) % K != 0)
+    return fail(ASSET_HIP_EINVAL, "the trajectory must hold nb*(cs-1)+1 nodes with nb >= 1 blocks");
+  const int nb = (nnodes - 1) / K;
+  for (size_t i = 0, e = size_t(nnodes) * N; i < e; i++)
+    if (!std::isfinite(traj[i])) return fail(ASSET_HIP_EINVAL, "NaN or Inf in the trajectory");
+  // the reference's two checkInput errors (LGLInterpTable.h:147-165)
+  const double dirn = traj[size_t(nnodes - 1) * N + n] - traj[n];
+  for (int j = 0; j + 1 < nnodes; j++) {
+    const double d = traj[size_t(j + 1) * N + n] - traj[size_t(j) * N + n];
+    if (d == 0.0) return fail(ASSET_HIP_EINVAL, "the trajectory holds duplicate times (node " + std::to_string(j) + ")");
+    if ((d > 0.0) != (dirn > 0.0)) return fail(ASSET_HIP_EINVAL, "the trajectory's times are not monotonic (node " + std::to_string(j) + ")");
+  }
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
+    return fail(ASSET_HIP_ENODEV, "no HIP device visible: the trajectory table has no CPU fallback");
+  if (device < 0 || device >= ndev) return fail(ASSET_HIP_EINVAL, "device ordinal out of range");
+  HIP_TRY(hipSetDevice(device));
+  std::unique_ptr<asset_hip_traj_table> t(new (std::nothrow) asset_hip_traj_table());
+  if (!t) return fail(ASSET_HIP_EINVAL, "out of host memory");
+  t->ke = ke, t->nb = nb, t->nnodes = nnodes, t->N = N, t->n = n, t->device = device;
+  t->t0 = traj[n], t->tf = traj[size_t(nnodes - 1) * N + n];
+  hipDeviceProp_t prop;
+  if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0) t->cus = prop.multiProcessorCount;
+  const size_t sz_traj = size_t(nnodes) * N, sz_xd = size_t(nnodes) * n, total = sz_traj + sz_xd + size_t(nb) + 1;
+  auto bail = [&](int rc) {
+    if (t->d_buf) (void)hipFree(t->d_buf);
+    if (t->d_count) (void)hipFree(t->d_count);
+    if (t->stream) (void)hipStreamDestroy(t->stream);
+    return rc;
+  };
+  hipError_t e;
+  if ((e = hipStreamCreateWithFlags(&t->stream, hipStreamNonBlocking)) != hipSuccess) return bail(hipfail(e, "hipStreamCreate"));
+  if ((e = hipMalloc(&t->d_buf, total * sizeof(double))) != hipSuccess) return bail(hipfail(e, "hipMalloc(table)"));
+  if ((e = hipMalloc(&t->d_count, sizeof(unsigned long long))) != hipSuccess) return bail(hipfail(e, "hipMalloc(counter)"));
+  t->a.nb = nb, t->a.nq = 0;
+  t->a.traj = t->d_buf, t->a.xdot = t->d_buf + sz_traj, t->a.tb = t->d_buf + sz_traj + sz_xd;
+  if ((e = hipMemcpyAsync(t->d_buf, traj, sz_traj * sizeof(double), hipMemcpyHostToDevice, t->stream)) != hipSuccess)
+    return bail(hipfail(e, "hipMemcpy(traj)"));
+  if ((e = asset_hip::entry_interp_table(ke, t->a, t->stream)) != hipSuccess) return bail(hipfail(e, "interp_xdot_kernel"));
+  if ((e = hipStreamSynchronize(t->stream)) != hipSuccess) return bail(hipfail(e, "trajectory table set-up"));
+  *out = t.release();
+  return 0;
+}
+
+static int traj_table_launch(asset_hip_traj_table_t t, const double* d_times, long long n, int deriv, double* d_out,
+                             double* d_dout, unsigned long long* d_count, hipStream_t st) {
+  asset_hip::InterpArgs a = t->a;
+  a.nq = n, a.times = d_times, a.out = d_out, a.dout = deriv ? d_dout : nullptr, a.n_outside = d_count;
+  const hipError_t e = asset_hip::entry_interp(t->ke, a, t->cus, st);
+  if (e != hipSuccess) return hipfail(e, "interp_eval_kernel");
+  return 0;
+}
+
+int asset_hip_traj_table_interp_device(asset_hip_traj_table_t t, const double* d_times, long long n, int deriv, double* d_out,
+                                       double* d_dout, unsigned long long* d_n_outside, void* stream) {
+  if (!t) return fail(ASSET_HIP_EINVAL, "null table");
+  if (n < 0 || (n > 0 && (!d_times || !d_out)) || (deriv && n > 0 && !d_dout)) return fail(ASSET_HIP_EINVAL, "bad interpolation arguments");
+  HIP_TRY(hipSetDevice(t->device));
+  return traj_table_launch(t, d_times, n, deriv, d_out, d_dout, d_n_outside, stream ? static_cast<hipStream_t>(stream) : t->stream);
+}
+
+int asset_hip_traj_table_interp(asset_hip_traj_table_t t, const double* times, long long n, int deriv, double* out, double* dout,
+                                long long* n_outside) {
+  if (!t) return fail(ASSET_HIP_EINVAL, "null table");
+  if (n < 0 || (n > 0 && (!times || !out)) || (deriv && n > 0 && !dout)) return fail(ASSET_HIP_EINVAL, "bad interpolation arguments");
+  if (n_outside) *n_outside = 0;
+  if (n == 0) return 0;
+  for (long long i = 0; i < n; i++)
+    if (!std::isfinite(times[i])) return fail(ASSET_HIP_EINVAL, "NaN or Inf among the query times");
+  HIP_TRY(hipSetDevice(t->device));
+  const size_t N = size_t(t->N);
+  if (n > t->cap_q) {   // times | out | dout
+    HIP_TRY(hipStreamSynchronize(t->stream));
+    if (t->d_stage) (void)hipFree(t->d_stage);
+    t->d_stage = nullptr, t->cap_q = 0;
+    HIP_TRY(hipMalloc(&t->d_stage, size_t(n) * (1 + 2 * N) * sizeof(double)));
+    t->cap_q = n;
+  }
+  double *d_times = t->d_stage, *d_out = d_times + t->cap_q, *d_dout = d_out + size_t(t->cap_q) * N;
+  HIP_TRY(hipMemcpyAsync(d_times, times, size_t(n) * sizeof(double), hipMemcpyHostToDevice, t->stream));
+  HIP_TRY(hipMemsetAsync(t->d_count, 0, sizeof(unsigned long long), t->stream));
+  const int rc = traj_table_launch(t, d_times, n, deriv, d_out, d_dout, t->d_count, t->stream);
+  if (rc) return rc;
+  HIP_TRY(hipMemcpyAsync(out, d_out, size_t(n) * N * sizeof(double), hipMemcpyDeviceToHost, t->stream));
+  if (deriv) HIP_TRY(hipMemcpyAsync(dout, d_dout, size_t(n) * N * sizeof(double), hipMemcpyDeviceToHost, t->stream));
+  unsigned long long cnt = 0;
+  HIP_TRY(hipMemcpyAsync(&cnt, t->d_count, sizeof cnt, hipMemcpyDeviceToHost, t->stream));
+  HIP_TRY(hipStreamSynchronize(t->stream));
+  if (n_outside) *n_outside = (long long)cnt;
+  return 0;
+}
+
+int asset_hip_traj_table_info(asset_hip_traj_table_t t, int* nblocks, int* ncols, double* t0, double* tf) {
+  if (!t) return fail(ASSET_HIP_EINVAL, "null table");
+  if (nblocks) *nblocks = t->nb;
+  if (ncols) *ncols = t->N;
+  if (t0) *t0 = t->t0;
+  if (tf) *tf = t->tf;
+  return 0;
+}
+
+void asset_hip_traj_table_destroy(asset_hip_traj_table_t t) {
+  if (!t) return;
+  (void)hipSetDevice(t->device);
+  if (t->stream) (void)hipStreamSynchronize(t->stream);
+  (void)hipDeviceSynchronize();          // (queries enqueued on the caller's streams still read the table)
+  if (t->d_buf) (void)hipFree(t->d_buf);
+  if (t->d_stage) (void)hipFree(t->d_stage);
+  if (t->d_count) (void)hipFree(t->d_count);
+  if (t->stream) (void)hipStreamDestroy(t->stream);
+  delete t;
 }
 
 // ---------------------------------------------------------------------------------------------- on-device assembly

@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "kernel_meta.h"
+#include "interp_kernels.h"
 #include "mesh_kernels.h"
 
 namespace asset_hip {
@@ -129,7 +130,8 @@ constexpr int K_ROWS1 = 59;    // ... the Jacobian kinds
 constexpr int K_UNITS4 = 60;   // heavy right-hand sides: interior and cardinal units in one launch (defect_units.h, PHASE 4)
 constexpr int K_RESLP = 61;   // resident kernel, looped, level 2, blocks, as two-wave workgroups (row-wise dense part: defect_rowdpp.h)
 constexpr int K_RES_ALT = 62;   // resident kernel, one group, level 2, blocks: the row-wise dense part of a shape that defaults to tiles
-constexpr int K_COUNT = 63;
+constexpr int K_INTERP_XDOT = 63, K_INTERP_EVAL = 64;   // trajectory table (interp_kernels.h): right-hand side at every node, evaluation at query times
+constexpr int K_COUNT = 65;
 
 struct KernelTable {
   long long meta[MF_COUNT] = {};
@@ -426,6 +428,24 @@ inline hipError_t entry_mesh(const KernelEntry* ke, const MeshArgs& a, hipStream
   return klaunch(ke->table->k[K_MESH_ERROR], dim3(grid), dim3(64), 0, st, eargs);
 }
 
+// trajectory table (interp_kernels.h); only transcriptions of an ODE have it.  entry_interp_table: stage 1 (a.traj -> a.xdot, a.tb),
+// entry_interp: stage 2 (a.times -> a.out, a.dout)
+inline bool entry_has_interp(const KernelEntry* ke) { return bool(ke->table->k[K_INTERP_XDOT]) && bool(ke->table->k[K_INTERP_EVAL]); }
+inline hipError_t entry_interp_table(const KernelEntry* ke, const InterpArgs& a, hipStream_t st) {
+  InterpArgs args = a;
+  void* kargs[] = {&args};
+  const long long nodes = (long long)a.nb * (interp_basis(ke->mode).cs - 1) + 1;
+  return klaunch(ke->table->k[K_INTERP_XDOT], dim3(unsigned((nodes + 63) / 64)), dim3(64), 0, st, kargs);
+}
+inline hipError_t entry_interp(const KernelEntry* ke, const InterpArgs& a, int cus, hipStream_t st) {
+  if (a.nq <= 0) return hipSuccess;
+  InterpArgs args = a;
+  void* kargs[] = {&args};
+  // memory-bound: at most 8 workgroups per CU, each walks its share of the query groups
+  const long long groups = (a.nq + INTERP_QG - 1) / INTERP_QG, cap = (long long)(cus > 0 ? cus : 256) * 8;
+  return klaunch(ke->table->k[K_INTERP_EVAL], dim3(unsigned(groups < cap ? groups : cap)), dim3(256), 0, st, kargs);
+}
+
 // per-lane constants of the dense stage for derivative level 1 / 2: table size in bytes (0: none) and the kernel filling it
 // (level 0 stands for the record of the resident kernel)
 inline size_t entry_lane_bytes(const KernelEntry* ke, int level) {
@@ -504,6 +524,8 @@ const KernelTable* lgl_static_table() {
     r.k[K_VALUE].host = ASSET_KPTR(lgl_adjgrad_kernel<Ode, SCH, BLOCKED, false>);
     r.k[K_MESH_YVEC].host = ASSET_KPTR(mesh_yvec_kernel<Ode, SCH, BLOCKED>);
     r.k[K_MESH_ERROR].host = ASSET_KPTR(mesh_error_kernel<0>);
+    r.k[K_INTERP_XDOT].host = ASSET_KPTR(interp_xdot_kernel<Ode, SCH, BLOCKED>);
+    r.k[K_INTERP_EVAL].host = ASSET_KPTR(interp_eval_kernel<Ode, SCH, BLOCKED>);
     return r;
   }();
   return &t;
@@ -596,6 +618,8 @@ inline std::string rtc_kernel_expr(int slot, int kind, const std::string& type, 
   if (slot == K_VALUE) return "asset_hip::lgl_adjgrad_kernel<" + lgl + ", false>";
   if (slot == K_MESH_YVEC) return "asset_hip::mesh_yvec_kernel<" + lgl + ">";
   if (slot == K_MESH_ERROR) return "asset_hip::mesh_error_kernel<0>";
+  if (slot == K_INTERP_XDOT) return "asset_hip::interp_xdot_kernel<" + lgl + ">";
+  if (slot == K_INTERP_EVAL) return "asset_hip::interp_eval_kernel<" + lgl + ">";
   return "";
 }
 

@@ -27,6 +27,7 @@ from .indexing import PhaseIndexer
 
 _MODES = ("LGL3", "LGL5", "LGL7", "Trapezoidal")
 _CONTROL_MODES = ("HighestOrderSpline", "FirstOrderSpline", "NoSpline", "BlockConstant")
+_TRAJ_INTERPOLATIONS = ("linear", "transcription")
 
 
 class DefectFunction:
@@ -118,6 +119,7 @@ class Phase:
         self._auto_evs = {}       # "mesh_spacing", "nodal_spacing", "control_spline": evaluators the phase adds itself
         self.EnableHessianSparsity = False   # Trapezoidal only (ODEPhase.h:43, TrapezoidalDefects.h:39): see hessian_mask()
         self.EnableMeshSpacing = True      # (the reference always adds them; the switch is for callers that only want the defects)
+        self.TrajInterpolation = "linear"  # how refineTrajManual / updateMesh carry the trajectory onto a new mesh: setTrajInterpolation
 
     # ---- configuration ---------------------------------------------------------------------
     def switchTranscriptionMode(self, mode: str):
@@ -133,6 +135,14 @@ class Phase:
             raise ValueError(f"Unrecognized control mode: {mode}")
         self.ControlMode = mode
         self._ev = None
+
+    def setTrajInterpolation(self, kind: str):
+        """How ``refineTrajManual`` (hence ``updateMesh``) re-distributes the active trajectory on a new mesh: ``"linear"`` (the
+        default: column-wise linear interpolation in time on the host) or ``"transcription"`` (the reference's behaviour: the
+        transcription's own Hermite polynomial through the device trajectory table, ``returnTrajTable``)."""
+        if kind not in _TRAJ_INTERPOLATIONS:
+            raise ValueError(f"Unrecognized trajectory interpolation: {kind!r} (expected one of {_TRAJ_INTERPOLATIONS})")
+        self.TrajInterpolation = kind
 
     # ---- AutoScaling: the dynamics in scaled units (ODEPhase.h:87-109 setUnits, :293-326 transcribe_dynamics) --
     def setUnits(self, XtUPUnits):
@@ -203,23 +213,54 @@ class Phase:
     def _mesh_times(self, DBS, DPB, t0, tf):
         """Times of the K * numDefects + 1 states of the mesh: bin i spans [DBS[i], DBS[i+1]] of [t0, tf], its DPB[i]
         segments are equal, the states of a segment sit at the scheme's cardinal spacing."""
-        cs = synth.MODE_CS[self.TranscriptionMode]
-        tc, K = _lib.lgl_table(cs, "tc"), cs - 1
-        edges = np.concatenate([np.linspace(DBS[i], DBS[i + 1], DPB[i] + 1)[(1 if i else 0):] for i in range(DPB.size)])
-        edges = t0 + (edges - DBS[0]) / (DBS[-1] - DBS[0]) * (tf - t0)
-        nodes = np.empty(K * (edges.size - 1) + 1)
-        for j in range(K):
-            nodes[j:-1:K] = edges[:-1] + tc[j] * (edges[1:] - edges[:-1])
-        nodes[-1] = tf
-        return nodes
+        from .interp import distribute_times      # (one definition: the trajectory table's NDdistribute uses the same times)
+        return distribute_times(self.TranscriptionMode, DBS, DPB, t0, tf)
 
     def refineTrajManual(self, DefBinSpacing, DefsPerBin):
-        """Re-distribute the active trajectory on new bins (ODEPhaseBase.cpp:662-677; the adaptive mesh loop's re-meshing step,
-        :1443-1542 -- the interpolation is linear here, the reference's is the transcription's own polynomial)."""
+        """Re-distribute the active trajectory on new bins (ODEPhaseBase.cpp:673-688; the adaptive mesh loop's re-meshing step,
+        :1443-1542).  With ``setTrajInterpolation("linear")`` (the default) the interpolation is linear in time, column by column;
+        with ``"transcription"`` it is the reference's: the active trajectory is loaded into the device trajectory table (the ODE
+        right-hand side at every node: the unscaled ODE and trajectory, BlockConstant from the control mode) and the degree
+        2 CS - 1 Hermite polynomial of each segment is evaluated at the new node times (``Table.NDdistribute``)."""
         if self.ActiveTraj is None:
             raise RuntimeError("No trajectory set: call setTraj first")
-        self.setTraj(self.ActiveTraj, DefBinSpacing, DefsPerBin)
+        if self.TrajInterpolation == "linear":
+            self.setTraj(self.ActiveTraj, DefBinSpacing, DefsPerBin)
+            return self.returnTraj()
+        DBS, DPB = np.asarray(DefBinSpacing, dtype=float).ravel(), np.asarray(DefsPerBin, dtype=int).ravel()
+        self._check_bins(DBS, DPB)
+        with self.returnTrajTable() as table:
+            nodes = self._mesh_times(DBS, DPB, table.T0, table.TF)
+            out = table.Interpolate(nodes)
+        out[:, self.ode.TVar()] = nodes      # (the node times themselves, as setTraj leaves them: T0 and TF do not drift over re-meshings)
+        self.ActiveTraj = out
+        self.DefBinSpacing, self.DefsPerBin = DBS.copy(), DPB.copy()
+        self.numDefects = int(DPB.sum())
+        self._ev = None
         return self.returnTraj()
+
+    # ---- the trajectory table (ODEPhaseBase.h:1025-1037) ---------------------------------------------------------
+    def returnTrajTable(self):
+        """The active trajectory as a device trajectory table (:class:`~asset_asrl_amd.interp.LGLInterpTable`, exact data: the
+        phase's transcription, the unscaled ODE, BlockConstant from the control mode).  The caller closes it (or uses ``with``)."""
+        from .interp import LGLInterpTable
+        if self.ActiveTraj is None:
+            raise RuntimeError("No trajectory set: call setTraj first")
+        return LGLInterpTable(self.ode, self.ActiveTraj, self.TranscriptionMode, self._blocked(), self.device)
+
+    def returnTrajRange(self, n: int, tl: float, th: float):
+        """The ``n K + 1`` cardinal-spaced states of ``n`` equal segments between the times ``tl`` and ``th``, from the trajectory
+        table.  One deliberate difference from the reference: its ``returnTrajRange`` first re-samples the active trajectory onto an
+        even mesh of the same segment count (``loadRegularData``, LGLInterpTable.h:322-348) and interpolates that; here the exact
+        table of the active trajectory is evaluated directly -- the same polynomial on an even mesh, strictly closer to the
+        solution on a ragged one."""
+        with self.returnTrajTable() as table:
+            return [row.copy() for row in table.InterpRange(n, tl, th)]
+
+    def returnTrajRangeND(self, n: int, lo: float, hi: float):
+        """``returnTrajRange`` between the non-dimensional times ``lo`` and ``hi`` (0: first, 1: last time of the trajectory)."""
+        with self.returnTrajTable() as table:
+            return [row.copy() for row in table.NDequidist(n, lo, hi)]
 
     def _nodal_spacing(self):
         """Non-dimensional times of the nodal states (segment boundaries), from the phase's own bins -- whatever the active
@@ -613,8 +654,9 @@ class Phase:
     def updateMesh(self):
         """The next mesh from the last iterate: per segment (err * MeshErrFactor / MeshTol)^(1 / (Order + 1)) new segments (at least
         MeshRedFactor), summed, plus NumExtraSegs, kept between MeshRedFactor and MeshIncFactor times the current number and
-        between MinSegments and MaxSegments; their edges equidistribute the error density; the trajectory is re-distributed
-        (control-switch detection, :1511-1536, is not built)."""
+        between MinSegments and MaxSegments; their edges equidistribute the error density; the trajectory is re-distributed by
+        ``refineTrajManual`` -- linearly, or with ``setTrajInterpolation("transcription")`` through the trajectory table as the
+        reference does (control-switch detection, :1511-1536, is not built)."""
         if not self.MeshIters:
             raise RuntimeError("checkMesh first")
         it = self.MeshIters[-1]

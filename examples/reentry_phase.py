@@ -36,6 +36,9 @@ print(f"segment 0: |d| = {np.abs(fx[0]).max():.3e}, J {J.shape}, H {H.shape}, |J
 tsnd, bins, err = phase.getMeshInfo(False, nsegs)
 print(f"de Boor mesh error: max {err.max():.3e} at t/T = {tsnd[err.argmax()]:.3f}")
 
+mid = phase.returnTrajRange(1, 0.45 * float(phase.ActiveTraj[-1, 5]), 0.55 * float(phase.ActiveTraj[-1, 5]))   # the trajectory
+print(f"returnTrajRange (device trajectory table, LGL7 Hermite interpolant): {len(mid)} states, first {np.round(mid[0], 4)}")   # table
+
 defect = phase.get_defect()                                       # one segment as a VectorFunction: z[IR] -> d[OR]
 fx1, jx1, gx1, hx1 = defect.computeall(X[ev.vindex[0]], L[:ev.OR])
 print(f"get_defect().computeall: fx {fx1.shape} jx {jx1.shape} gx {gx1.shape} hx {hx1.shape}")

@@ -262,6 +262,37 @@ int asset_hip_defect_time_device(asset_hip_defect_t h, int what, const double* d
 int asset_hip_mesh_error_deboor(const char* ode, int mode, int blocked, const double* traj, int nnodes, double* tsnd,
                                 double* mesh_errors, double* mesh_dist, double* error_max, double* dist_max, int device);
 
+/* ---- trajectory table: the transcription's own Hermite interpolant of a phase trajectory, on the device ----
+ * Replaces LGLInterpTable for exact data (OptimalControl/LGLInterpTable.h:349-372, 480-669, 866-926), the table behind
+ * ODEPhaseBase::refineTrajManual / updateMesh / returnTrajRange / returnTrajRangeND / returnTrajTable
+ * (ODEPhaseBase.cpp:673-688, ODEPhaseBase.h:1025-1037).
+ *   create   traj (host): [nnodes][XV+1+UV+PV] row-major node rows [x,t,u,p], nnodes = nb*(cs-1)+1 with nb >= 1 blocks, times
+ *            strictly monotonic in either direction, all values finite.  Trapezoidal uses the LGL3 (cubic) table.  The ODE
+ *            right-hand side is evaluated once at every node (each row with its own controls) and stays resident with the
+ *            trajectory and the block start times, so a query costs the evaluation only.  `blocked` != 0: BlockConstant
+ *            control (the reference's Table.BlockedControls).
+ *   interp   n query times (host) -> out[n][N]: block by binary search -- a time on an interior block boundary belongs to the
+ *            block it ends, a time outside the data extrapolates from the first / last block and is counted in *n_outside
+ *            (may be NULL) --, s = (t - t_first) / h, states = sum_i X_i phi_i(s) + h sum_i f_i psi_i(s) (degree 2cs-1), time
+ *            entry t_first + h s, controls and ODE parameters = sum_i U_i ups_i(s) (degree cs-1) or, blocked, those of the
+ *            block's first row.  deriv != 0: dout[n][N] receives d/dt of all of it (time entry 1; blocked controls and
+ *            parameters 0, the derivative of what `out` holds -- the reference's InterpolateDeriv ignores BlockedControls).
+ *   interp_device  the same with device pointers (d_n_outside: one unsigned 64-bit device counter, ADDED to, may be NULL), enqueued
+ *            on `stream` (NULL = the table's own stream, ASSET_HIP_STREAM_LEGACY as above) and NOT synchronised; create returns
+ *            synchronised, so a query on any stream sees the finished table.
+ *   info     blocks, columns N, first and last time.
+ * Errors: ASSET_HIP_ENOODE (no device code for the entry), ASSET_HIP_EINVAL (entry without the table kernels, nnodes-1 not a
+ * multiple of cs-1, no block, duplicate or non-monotonic times, non-finite input), ASSET_HIP_ENODEV. */
+typedef struct asset_hip_traj_table* asset_hip_traj_table_t;
+int asset_hip_traj_table_create(const char* ode, int mode, int blocked, const double* traj, int nnodes, int device,
+                                asset_hip_traj_table_t* out);
+int asset_hip_traj_table_interp(asset_hip_traj_table_t t, const double* times, long long n, int deriv, double* out,
+                                double* dout, long long* n_outside);
+int asset_hip_traj_table_interp_device(asset_hip_traj_table_t t, const double* d_times, long long n, int deriv, double* d_out,
+                                       double* d_dout, unsigned long long* d_n_outside, void* stream);
+int asset_hip_traj_table_info(asset_hip_traj_table_t t, int* nblocks, int* ncols, double* t0, double* tf);
+void asset_hip_traj_table_destroy(asset_hip_traj_table_t t);
+
 /* ---- introspection ---- */
 int asset_hip_num_odes(void);
 const char* asset_hip_ode_name(int i);                           /* NULL when i is out of range            */
