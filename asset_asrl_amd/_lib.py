@@ -28,6 +28,15 @@ class DefectDesc(C.Structure):
                 ("device", C.c_int)]
 
 
+class PlanStep(C.Structure):
+    _fields_ = [("slot", C.c_int), ("grid_x", C.c_int), ("grid_y", C.c_int), ("block", C.c_int), ("lds_bytes", C.c_longlong),
+                ("extra_arg", C.c_int), ("group", C.c_int)]
+
+
+class LaunchPlan(C.Structure):
+    _fields_ = [("nsteps", C.c_int), ("units_gp", C.c_int), ("step", PlanStep * 3)]
+
+
 # every symbol include/asset_hip.h declares: name -> (restype, argtypes)
 SYMBOLS = {
     "asset_hip_defect_create": (C.c_int, [C.POINTER(DefectDesc), C.POINTER(C.c_void_p)]),
@@ -37,6 +46,10 @@ SYMBOLS = {
     "asset_hip_defect_kkt_layout": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "asset_hip_kkt_layout": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int32),
                                       C.POINTER(C.c_int32)]),
+    "asset_hip_launch_plan_query": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(LaunchPlan)]),
+    "asset_hip_defect_launch_plan": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(LaunchPlan)]),
+    "asset_hip_kernel_slot_name": (C.c_char_p, [C.c_int]),
+    "asset_hip_kernel_slot_kinds": (C.c_int, [C.c_int]),
     "asset_hip_defect_eval": (C.c_int, [C.c_void_p, C.c_int, _dp, _dp, _dp, _dp, _dp]),
     "asset_hip_defect_eval_device": (C.c_int, [C.c_void_p, C.c_int] + [C.c_void_p] * 6),
     "asset_hip_jit_compile": (C.c_int, [C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_char_p),
@@ -134,6 +147,22 @@ def kkt_layout(name: str, mode: int, blocked: bool):
     if kl < 0:
         check(kl, "asset_hip_kkt_layout")
     return kl, nk.value, st.value, rows, cols
+
+
+def _plan_rows(p: LaunchPlan):
+    L = lib()
+    steps = [(L.asset_hip_kernel_slot_name(s.slot).decode(), s.grid_x, s.grid_y, s.block, s.lds_bytes, s.extra_arg, s.group)
+             for s in p.step[:p.nsteps]]
+    return steps, p.units_gp
+
+
+def launch_plan(name: str, mode: int, blocked: bool, what: int, assembled: bool, nseg: int, cus: int = 256):
+    """([(kernel slot name, grid x, grid y, block, LDS bytes, extra argument, group)], units_gp): what one evaluation of a compiled
+    (ode, mode, blocked) launches on a device of ``cus`` compute units: asset_hip_launch_plan_query -- no handle, no device."""
+    p = LaunchPlan()
+    check(lib().asset_hip_launch_plan_query(name.encode(), mode, int(blocked), what, int(assembled), nseg, cus, C.byref(p)),
+          "asset_hip_launch_plan_query")
+    return _plan_rows(p)
 
 
 def has_kernel(name: str, mode: int, blocked: bool) -> bool:

@@ -200,7 +200,7 @@ struct RtcBlob {
   std::vector<std::pair<int, std::string>> names;
   std::vector<char> code;
 };
-const char kRtcMagic[] = "ASSET-HIP-RTC-1";
+const char kRtcMagic[] = "ASSET-HIP-RTC-1";   // (slot numbers are those of registry.h: a module is cached under a digest of csrc/*.h, asset_asrl_amd/jit.py)
 
 bool rtc_write(const std::string& path, const RtcBlob& b) {
   const std::string tmp = path + ".tmp" + std::to_string(long(getpid()));
@@ -602,6 +602,45 @@ int asset_hip_kkt_layout(const char* ode, int mode, int blocked, int* nkkt, int*
   return entry_kkt_layout(ke, stride, rows, cols);
 }
 
+// The launch plan (registry.h: plan_lgl) of one evaluation kind, with the default dispatch -- what a handle of `nseg` segments on
+// a device of `cus` compute units launches when no tuning knob is in effect
+static int entry_launch_plan(const asset_hip::KernelEntry* ke, int what, int assembled, int nseg, int cus, bool res_record,
+                             asset_hip_launch_plan* out) {
+  const int level = level_of(what);
+  if (!out || level < 0 || (what & ~0xff) || (assembled && what < ASSET_HIP_JAC)) return fail(ASSET_HIP_EINVAL, "bad launch plan query");
+  if (ke->table->meta[asset_hip::MF_KIND] != 1) return fail(ASSET_HIP_EINVAL, "launch plans are those of the transcriptions of an ODE");
+  const bool adj = what == ASSET_HIP_CON_ADJGRAD || what == ASSET_HIP_JAC_ADJGRAD || what == ASSET_HIP_JAC_ADJGRAD_HESS;
+  asset_hip::LaunchPlan p;
+  if (asset_hip::plan_lgl(*ke->table, asset_hip::PlanRequest{level, what >= ASSET_HIP_JAC && !assembled, assembled != 0, adj, res_record},
+                          nseg, cus, asset_hip::Tuning(), p) != hipSuccess)
+    return fail(ASSET_HIP_EINVAL, "bad launch plan query (nseg and cus are positive)");
+  *out = asset_hip_launch_plan();
+  out->nsteps = p.nsteps, out->units_gp = p.units_gp;
+  for (int i = 0; i < p.nsteps; i++) {
+    const asset_hip::PlanStep& s = p.step[i];
+    if (!ke->table->k[s.slot]) return fail(ASSET_HIP_ENOODE, std::string("the plan names a kernel this shape lacks: ") + asset_hip::kslot_name(s.slot));
+    out->step[i] = asset_hip_plan_step{s.slot, int(s.grid_x), int(s.grid_y), int(s.block), (long long)s.lds_bytes, s.extra, s.gp};
+  }
+  return 0;
+}
+int asset_hip_launch_plan_query(const char* ode, int mode, int blocked, int what, int assembled, int nseg, int cus,
+                                asset_hip_launch_plan* out) {
+  const asset_hip::KernelEntry* ke = ode ? find_entry(ode, mode, blocked) : nullptr;
+  if (!ke) return fail(ASSET_HIP_ENOODE, "no device code compiled for this (ode, mode, blocked)");
+  return entry_launch_plan(ke, what, assembled, nseg, cus, asset_hip::entry_lane_bytes(ke, 0) > 0, out);
+}
+int asset_hip_defect_launch_plan(asset_hip_defect_t h, int what, int assembled, asset_hip_launch_plan* out) {
+  if (!h) return fail(ASSET_HIP_EINVAL, "null handle");
+  return entry_launch_plan(h->ke, what, assembled, h->nseg, h->cus, h->d_lane[0] != nullptr, out);
+}
+const char* asset_hip_kernel_slot_name(int slot) { return asset_hip::kslot_name(slot); }
+int asset_hip_kernel_slot_kinds(int slot) {
+  int kinds = 0;
+  for (int kind = 1; kind <= 3; kind++)
+    if (!asset_hip::rtc_kernel_expr(slot, kind, "F", ASSET_HIP_LGL3, false, 1).empty()) kinds |= 1 << (kind - 1);
+  return kinds;
+}
+
 // the kernel arguments of one evaluation of a handle (block kinds)
 static int fill_args(asset_hip_defect_t h, int what, const double* dX, const double* dL, double* dfx, double* dagx,
                      double* dkkt, asset_hip::EvalArgs& a) {
@@ -630,8 +669,7 @@ static int fill_args(asset_hip_defect_t h, int what, const double* dX, const dou
   a.work = h->d_work;
   a.lane_consts = level >= 1 ? h->d_lane[level] : nullptr;
   a.lane_consts_res = h->d_lane[0];
-  static const bool no_affine = asset_hip::tuning_env("ASSET_HIP_NO_AFFINE") != nullptr;                                // tuning only
-  a.affine = no_affine ? 0 : h->affine, a.aff_v0 = h->aff_v0, a.aff_vs = h->aff_vs, a.aff_c0 = h->aff_c0, a.aff_cs = h->aff_cs;
+  a.affine = asset_hip::tuning().no_affine ? 0 : h->affine, a.aff_v0 = h->aff_v0, a.aff_vs = h->aff_vs, a.aff_c0 = h->aff_c0, a.aff_cs = h->aff_cs;
   a.appl_consts = h->d_aconst;
   if (h->ke->naconst > 0 && !h->d_aconst)
     return fail(ASSET_HIP_EINVAL, "this function reads constants of its applications: call asset_hip_defect_set_appl_consts first");
@@ -727,7 +765,8 @@ int asset_hip_bundle_eval_device(asset_hip_bundle_t b, int what, const double* d
   for (int k = n; k <= asset_hip::BUNDLE_MAX; k++) args.start[k] = blocks;
   void* kargs[] = {&args};
   hipStream_t st = stream ? static_cast<hipStream_t>(stream) : b->members[0]->stream;
-  hipError_t e = asset_hip::klaunch(b->ke->table->k[asset_hip::K_BUNDLE(level)], dim3(blocks), dim3(64), shmem, st, kargs);
+  const int slot = level == 0 ? asset_hip::K_BUNDLE0 : (level == 1 ? asset_hip::K_BUNDLE1 : asset_hip::K_BUNDLE2);
+  hipError_t e = asset_hip::klaunch(b->ke->table->k[slot], dim3(blocks), dim3(64), shmem, st, kargs);
   if (e != hipSuccess) return hipfail(e, "bundle launch");
   return 0;
 }

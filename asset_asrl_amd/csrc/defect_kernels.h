@@ -77,7 +77,7 @@ __device__ __attribute__((noinline)) void interior_eval(double* S, lds_double* M
 #pragma unroll
   for (int k = 0; k < p; k++) y[q + k] = z[D::P0 + k];
 #pragma unroll
-  for (int k = 0; k < n; k++) li[k] = (LEVEL >= 1) ? pin.lam[i * n + k] : 0.0;
+  for (int k = 0; k < n; k++) li[k] = pin.lam[i * n + k];
   RegIn<D> in{y, li};
   // g^_i feeds the adjoint weights of P3 (mirror copy); f^_i is only read by the dense stage
   OdeOutStaged<D, LEVEL == 1, false, false, MIR && LEVEL >= 2> out{S + D::w_If + i * n, S + D::w_Ig + i * N,
@@ -85,8 +85,7 @@ __device__ __attribute__((noinline)) void interior_eval(double* S, lds_double* M
                                                                    stage_or<D>(row + D::NZJ, S + D::w_IH + i * D::NZH)};
   if constexpr (MIR && LEVEL >= 2) out.g2_ = M + D::m_Ig + i * N;
   (void)K;
-  if constexpr (LEVEL == 0) Ode::f(in, out);
-  else if constexpr (LEVEL == 1) {
+  if constexpr (LEVEL == 1) {
     out.lamv_ = li;
     Ode::fj(in, out);
 #pragma unroll
@@ -138,8 +137,7 @@ __device__ inline void cardinal_eval1_body(const In& in, double* S, lds_double* 
     out.sv_ = S + D::w_SV + j * Ode::NSAVE;
   }
   if constexpr (LEVEL == 1) Ode::fj(in, out);
-  else if constexpr (LEVEL == 2) Ode::f_save(in, out);
-  else Ode::f(in, out);
+  else Ode::f_save(in, out);
 }
 
 template <class Ode, class D, int LEVEL, bool MIR>
@@ -750,7 +748,7 @@ __global__ __launch_bounds__(64) void lane_setup_kernel(unsigned int* out) {
 }
 
 // ---------------------------------------------------------------------------------------------- kernel
-// LEVEL 0: value only (constraints).  LEVEL 1: value + Jacobian (+ J^T lam).  LEVEL 2: + adjoint Hessian.
+// LEVEL 1: value + Jacobian (+ J^T lam).  LEVEL 2: + adjoint Hessian.  (Value only: defect_adjgrad.h.)
 // STAGE 1: ODE phases only (P0-P3; results -> workspace slot of every segment).  STAGE 2: dense phase only (P4).
 // They are separate launches because their resource shapes differ: the ODE bodies need ~250 VGPRs and wide LDS
 // staging rows, the dense phase needs few registers and 23 KiB of LDS, so it runs at a higher occupancy.
@@ -769,6 +767,7 @@ __device__ __forceinline__ void lgl_defect_body(const EvalArgs& a) {
   constexpr int LC = D::LC, NSTG = D::NSTG, STG_LD = D::STG_LD;
   static_assert(N == Ode::NIN, "ODE input size mismatch");
   static_assert(G * CS <= 64 * 8, "group too large");
+  static_assert(LEVEL == 1 || LEVEL == 2, "the value-only kind is lgl_adjgrad_kernel (defect_adjgrad.h)");
   (void)m; (void)p; (void)ORP;
 
   extern __shared__ __attribute__((aligned(16))) double lds[];
@@ -781,7 +780,7 @@ __device__ __forceinline__ void lgl_defect_body(const EvalArgs& a) {
   double* stage = body;
   static_assert(STAGE != 3 || (D::FUSED && LEVEL >= 1), "no fused kernel for this shape / level");
   static_assert(STAGE != 4 || (D::FUSED2 && LEVEL == 2), "no two-wave fused kernel for this shape / level");
-  constexpr bool MIR = D::MIRROR && LEVEL >= 1 && STAGE == 1;
+  constexpr bool MIR = D::MIRROR && STAGE == 1;
 #define ASSET_ODE_PIPE 1
   constexpr bool PIPE = ASSET_ODE_PIPE && MIR && LEVEL == 2 && D::STAGED && LC == 64 && G * CS <= 64;
   lds_double* const mirror = (lds_double*)(body + (STAGE == 3 ? D::GF * CS : LC) * STG_LD);   // [G][MSLOT] (ODE stage, MIR)
@@ -912,7 +911,7 @@ __device__ __forceinline__ void lgl_defect_body(const EvalArgs& a) {
     // Two dependent HBM round trips (index, then value): every index load is issued before the first value load,
     // so the whole gather costs two latencies instead of two per 64 elements.
     {
-      constexpr int NZ = (G * IR + 63) / 64, NL = (LEVEL >= 1) ? (G * OR + 63) / 64 : 0;
+      constexpr int NZ = (G * IR + 63) / 64, NL = (G * OR + 63) / 64;
       const int* vseg = a.vindex + size_t(seg0) * IR;      // this group's Vindex / Cindex columns are contiguous
       const int* cseg = a.cindex + size_t(seg0) * OR;
       int vi[NZ], ci[NL > 0 ? NL : 1];
@@ -977,7 +976,7 @@ __device__ __forceinline__ void lgl_defect_body(const EvalArgs& a) {
         const int g = e / K, i = e - g * K;
         interior_eval<Ode, D, LEVEL, MIR>(Wg + g * D::WSLOT, mirror + g * D::MSLOT, i, &tab, (lds_double*)(stage + lane * STG_LD));
       }
-      if constexpr (LEVEL >= 1 && D::STAGED) {
+      if constexpr (D::STAGED) {
         wave_lds_sync();   // staging rows are LDS-only hand-offs: do not wait for the global stores
         const int npt = min(LC, gcount * K - e0);
         constexpr int NC = (LEVEL >= 2) ? NSTG : D::NZJ;   // LEVEL 1 has no Hessian part
@@ -1010,26 +1009,8 @@ __device__ __forceinline__ void lgl_defect_body(const EvalArgs& a) {
       }
     }
 
-    if constexpr (LEVEL == 0) {
-      // ---- value only: lanes over (segment, defect row); everything needed is in the workspace slots
-      if (a.FX) {
-        for (int e = lane; e < gcount * OR; e += 64) {
-          const int g = e / OR, jr = e - g * OR;
-          const int i = jr / n, k = jr - i * n;
-          const double* S = Wg + g * D::WSLOT;
-          const double* z = S + D::w_z;
-          const double h = z[TF] - z[T];
-          double fxv = 0.0;
-#pragma unroll
-          for (int j = 0; j < CS; j++) fxv += (tab.C[i][j] * z[j * q + k] + (tab.D[i][j] * h) * S[D::w_Cf + j * n + k]);
-          fxv += (h * tab.E[i]) * S[D::w_If + i * n + k];
-          a.FX[size_t(seg0 + g) * OR + jr] = fxv;
-        }
-      }
-      wave_mem_sync();
-    }
     }  // STAGE == 1
-    if constexpr (STAGE == 1 || LEVEL == 0) continue;
+    if constexpr (STAGE == 1) continue;
 
     TS();
     constexpr int NPRE = (D::WSLOTD + 63) / 64;
@@ -1094,8 +1075,6 @@ __device__ __forceinline__ void lgl_defect_body(const EvalArgs& a) {
       const double h = z[TF] - z[T];
       const size_t seg = size_t(seg0 + g);
       TSG();   // slot in LDS
-
-      if constexpr (LEVEL == 0) continue;
 
       double* DIx = scr + D::s_DIx;
       const double* DIc = scr + D::s_DIc;

@@ -1,7 +1,7 @@
 // Kernel registry: every (ODE functor, transcription mode, blocked) instantiation compiled into libasset_hip.so registers
 // one entry; so does every module compiled at run time (capi.hip: asset_hip_jit_plugin).  The C ABI (capi.hip) looks
 // entries up by name at create time.  An entry is data -- the integers of kernel_meta.h and one reference per kernel
-// variant -- and ONE launcher (launch_lgl_table below) serves the kernels linked into the library (host stubs) and the
+// variant -- and ONE planner and launcher (plan_lgl, launch_plan below) serve the kernels linked into the library (host stubs) and the
 // kernels of a run-time module (hipFunction_t) alike.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -110,28 +110,85 @@ inline hipError_t klaunch(const KRef& k, dim3 grid, dim3 block, size_t shmem, hi
   return hipLaunchKernel(k.host, grid, block, args, shmem, st);
 }
 
-// kernel slots of a table (the same numbering for the static fill and for the name expressions of a run-time module)
-constexpr int K_LGL(int level, int stage, bool asmb) { return level * 8 + (stage - 1) * 2 + (asmb ? 1 : 0); }   // 0..23
-constexpr int K_WIDE(int level, bool asmb) { return 24 + (level - 1) * 2 + (asmb ? 1 : 0); }                     // 24..27
-constexpr int K_WIDE_SETUP = 28, K_LANE_SETUP1 = 29, K_LANE_SETUP2 = 30, K_UNITS0 = 31, K_UNITS1 = 32;
-constexpr int K_MESH_YVEC = 33, K_MESH_ERROR = 34;
-constexpr int K_FUNC(int level, bool asmb) { return 35 + level * 2 + (asmb ? 1 : 0); }                           // 35..40
-constexpr int K_BUNDLE(int level) { return 41 + level; }                                                         // 41..43
-constexpr int K_ADJGRAD = 44;   // value + adjoint gradient without a Jacobian (defect_adjgrad.h)
-constexpr int K_VALUE = 45;     // value only, the same kernel without the gradient parts
-constexpr int K_RES(bool asmb) { return 46 + (asmb ? 1 : 0); }   // resident single launch (defect_resident.h), level 2
-constexpr int K_RES_SETUP = 48;
-constexpr int K_RES1(bool asmb) { return 49 + (asmb ? 1 : 0); }  // ... the Jacobian kinds
-constexpr int K_RESL(int level, bool asmb) { return 51 + (level - 1) * 2 + (asmb ? 1 : 0); }   // ... looped over groups (large meshes)
-constexpr int K_RESD(bool asmb) { return 55 + (asmb ? 1 : 0); }   // ... its dense part alone, slots from the workspace (heavy ODEs)
-constexpr int K_UNITSJ = 57;   // heavy right-hand sides, Jacobian kinds: the unit kernel of the ODE stage (defect_units.h, PHASE 3)
-constexpr int K_ROWS = 58;     // wide shapes: dense stage by output rows, no matrix instructions (defect_rows.h)
-constexpr int K_ROWS1 = 59;    // ... the Jacobian kinds
-constexpr int K_UNITS4 = 60;   // heavy right-hand sides: interior and cardinal units in one launch (defect_units.h, PHASE 4)
-constexpr int K_RESLP = 61;   // resident kernel, looped, level 2, blocks, as two-wave workgroups (row-wise dense part: defect_rowdpp.h)
-constexpr int K_RES_ALT = 62;   // resident kernel, one group, level 2, blocks: the row-wise dense part of a shape that defaults to tiles
-constexpr int K_INTERP_XDOT = 63, K_INTERP_EVAL = 64;   // trajectory table (interp_kernels.h): right-hand side at every node, evaluation at query times
-constexpr int K_COUNT = 65;
+// ---- the kernels of a table: ONE list --------------------------------------------------------------------------------------
+// X(slot, family, condition, kernel template, trailing template arguments...).  The family says what precedes the trailing
+// arguments -- LGLG: <Ode, SCH, BLOCKED, G, ...>, LGL: <Ode, SCH, BLOCKED, ...>, NONE: <...> (all three: transcriptions of an ODE),
+// FUNC: <F, ...> (plain functions), BUNDLE: <..., Fs...> (bundles, run-time modules only) -- and the condition is the compile-time
+// one (D = Dims<Ode, SCH, BLOCKED>) under which a shape linked into the library has the kernel.  The slot enum, the static tables
+// (lgl_static_table, func_static_table) and the name expressions of a run-time module (rtc_kernel_expr, which names every slot of
+// its kind: rtc_device.h compiles the variants a shape lacks to empty kernels) are all generated from this list.
+#define ASSET_KERNELS(X)                                                                                                        \
+  /* defect_kernels.h: ODE stage (S1), dense stage (S2), both in one launch (S3), ... as two-wave workgroups (S4) */            \
+  X(K_LGL1_S1, LGLG, true, lgl_defect_kernel, 1, 1, false)                                                                      \
+  X(K_LGL2_S1, LGLG, true, lgl_defect_kernel, 2, 1, false)                                                                      \
+  X(K_LGL1_S2, LGLG, !D::WIDE, lgl_defect_kernel, 1, 2, false)                                                                  \
+  X(K_LGL1_S2_ASM, LGLG, !D::WIDE, lgl_defect_kernel, 1, 2, true)                                                               \
+  X(K_LGL2_S2, LGLG, !D::WIDE, lgl_defect_kernel, 2, 2, false)                                                                  \
+  X(K_LGL2_S2_ASM, LGLG, !D::WIDE, lgl_defect_kernel, 2, 2, true)                                                               \
+  X(K_LGL1_S3, LGLG, !D::WIDE && D::FUSED, lgl_defect_kernel, 1, 3, false)                                                      \
+  X(K_LGL1_S3_ASM, LGLG, !D::WIDE && D::FUSED, lgl_defect_kernel, 1, 3, true)                                                   \
+  X(K_LGL2_S3, LGLG, !D::WIDE && D::FUSED, lgl_defect_kernel, 2, 3, false)                                                      \
+  X(K_LGL2_S3_ASM, LGLG, !D::WIDE && D::FUSED, lgl_defect_kernel, 2, 3, true)                                                   \
+  X(K_LGL2_S4, LGLG, !D::WIDE && D::FUSED2, lgl_defect_kernel, 2, 4, false)                                                     \
+  X(K_LANE_SETUP1, LGL, !D::WIDE, lane_setup_kernel, 1)                                                                         \
+  X(K_LANE_SETUP2, LGL, !D::WIDE, lane_setup_kernel, 2)                                                                         \
+  /* wide shapes: dense stage of four-wave workgroups (defect_wide.h); by output rows, no matrix instructions (defect_rows.h) */ \
+  X(K_WIDE1, LGL, D::WIDE, lgl_wide_dense_kernel, 1, false)                                                                     \
+  X(K_WIDE1_ASM, LGL, D::WIDE, lgl_wide_dense_kernel, 1, true)                                                                  \
+  X(K_WIDE2, LGL, D::WIDE, lgl_wide_dense_kernel, 2, false)                                                                     \
+  X(K_WIDE2_ASM, LGL, D::WIDE, lgl_wide_dense_kernel, 2, true)                                                                  \
+  X(K_WIDE_SETUP, LGL, D::WIDE, wide_setup_kernel)                                                                              \
+  X(K_ROWS1, LGL, D::WIDE && RowsDims<D>::OK, lgl_rows_kernel, 1)                                                               \
+  X(K_ROWS2, LGL, D::WIDE && RowsDims<D>::OK, lgl_rows_kernel, 2)                                                               \
+  /* value + adjoint gradient without a Jacobian; value only: the same kernel without its gradient parts (defect_adjgrad.h) */  \
+  X(K_ADJGRAD, LGL, true, lgl_adjgrad_kernel, true)                                                                             \
+  X(K_VALUE, LGL, true, lgl_adjgrad_kernel, false)                                                                              \
+  /* resident single launch (defect_resident.h): one group per wave (RES), looped over groups (RESL), looped level-2 blocks as  \
+     two-wave workgroups with the row-wise dense part (RESLP: defect_rowdpp.h), one group with the row-wise dense part of a     \
+     shape that defaults to tiles (RES_ALT), the dense part alone over the slots the unit kernels wrote (RESD) */               \
+  X(K_RES1, LGL, !D::WIDE && ResDims<D>::OK, lgl_resident_kernel, 1, false)                                                     \
+  X(K_RES1_ASM, LGL, !D::WIDE && ResDims<D>::OK, lgl_resident_kernel, 1, true)                                                  \
+  X(K_RES2, LGL, !D::WIDE && ResDims<D>::OK, lgl_resident_kernel, 2, false)                                                     \
+  X(K_RES2_ASM, LGL, !D::WIDE && ResDims<D>::OK, lgl_resident_kernel, 2, true)                                                  \
+  X(K_RESL1, LGL, !D::WIDE && ResDims<D>::OK, lgl_resident_kernel, 1, false, true)                                              \
+  X(K_RESL1_ASM, LGL, !D::WIDE && ResDims<D>::OK, lgl_resident_kernel, 1, true, true)                                           \
+  X(K_RESL2, LGL, !D::WIDE && ResDims<D>::OK, lgl_resident_kernel, 2, false, true)                                              \
+  X(K_RESL2_ASM, LGL, !D::WIDE && ResDims<D>::OK, lgl_resident_kernel, 2, true, true)                                           \
+  X(K_RESLP, LGL, !D::WIDE && ResDims<D>::OK && ResDims<D>::LOOP_PAIR, lgl_resident_kernel, 2, false, true, false, true)        \
+  X(K_RES_ALT, LGL, !D::WIDE && ResDims<D>::OK && ResDims<D>::RD_ALT, lgl_resident_kernel, 2, false, false, false, false, 1)    \
+  X(K_RESD, LGL, !D::WIDE && ResDims<D>::GIVEN_OK, lgl_resident_kernel, 2, false, true, true)                                   \
+  X(K_RESD_ASM, LGL, !D::WIDE && ResDims<D>::GIVEN_OK, lgl_resident_kernel, 2, true, true, true)                                \
+  X(K_RES_SETUP, LGL, !D::WIDE && (ResDims<D>::OK || ResDims<D>::GIVEN_OK), res_lane_setup_kernel)                              \
+  /* heavy right-hand sides, one wave per output unit (defect_units.h): interior units, cardinal units, the ODE stage of the    \
+     Jacobian kinds (PHASE 3), interior and cardinal units in one launch (PHASE 4) */                                           \
+  X(K_UNITS0, LGL, (Ode::NUNITS > 1), lgl_ode_units_kernel, 0)                                                                  \
+  X(K_UNITS1, LGL, (Ode::NUNITS > 1), lgl_ode_units_kernel, 1)                                                                  \
+  X(K_UNITSJ, LGL, (Ode::NUNITS > 1), lgl_ode_units_kernel, 3)                                                                  \
+  X(K_UNITS4, LGL, (Ode::NUNITS > 1), lgl_ode_units_kernel, 4)                                                                  \
+  /* mesh error (mesh_kernels.h); trajectory table: right-hand side at every node, evaluation at query times (interp_kernels.h) */ \
+  X(K_MESH_YVEC, LGL, true, mesh_yvec_kernel)                                                                                   \
+  X(K_MESH_ERROR, NONE, true, mesh_error_kernel, 0)                                                                             \
+  X(K_INTERP_XDOT, LGL, true, interp_xdot_kernel)                                                                               \
+  X(K_INTERP_EVAL, LGL, true, interp_eval_kernel)                                                                               \
+  /* plain functions and bundles of them (func_kernels.h) */                                                                    \
+  X(K_FUNC0, FUNC, true, func_kernel, 0, false)                                                                                 \
+  X(K_FUNC1, FUNC, true, func_kernel, 1, false)                                                                                 \
+  X(K_FUNC1_ASM, FUNC, true, func_kernel, 1, true)                                                                              \
+  X(K_FUNC2, FUNC, true, func_kernel, 2, false)                                                                                 \
+  X(K_FUNC2_ASM, FUNC, true, func_kernel, 2, true)                                                                              \
+  X(K_BUNDLE0, BUNDLE, true, func_bundle_kernel, 0)                                                                             \
+  X(K_BUNDLE1, BUNDLE, true, func_bundle_kernel, 1)                                                                             \
+  X(K_BUNDLE2, BUNDLE, true, func_bundle_kernel, 2)
+
+#define ASSET_X_ENUM(NAME, ...) NAME,
+enum KSlot : int { ASSET_KERNELS(ASSET_X_ENUM) K_COUNT };
+#undef ASSET_X_ENUM
+#define ASSET_X_NAME(NAME, ...) #NAME,
+inline const char* kslot_name(int slot) {
+  static const char* const names[K_COUNT] = {ASSET_KERNELS(ASSET_X_NAME)};
+  return slot >= 0 && slot < K_COUNT ? names[slot] : nullptr;
+}
+#undef ASSET_X_NAME
 
 struct KernelTable {
   long long meta[MF_COUNT] = {};
@@ -192,208 +249,224 @@ struct Registrar {
 };
 #endif
 
-// ---- the launcher ---------------------------------------------------------------------------------------------------
-#define ASSET_UNITS_ONE_LAUNCH_ROUNDS 1000   // heavy ODEs: the one-launch unit stage ALWAYS (the limit, in rounds of the SIMDs, is beyond every mesh) -- measured faster at every size
-                                            // tried (Betts-LGL5 x 1 000: 30.3 against 41.5 us, x 10 000: 191.7 / 200.0; Betts-LGL7 x 5 000: 145.1 / 151.1)
-// Dispatch knobs of the measurement scripts (tools/): read ONLY when the process opts in with ASSET_HIP_TUNING=1, so that a
-// stray variable in a production environment cannot change which kernels run.  With the opt-in, every knob that takes effect is
-// reported once on stderr.
-inline const char* tuning_env(const char* name) {
-  static const bool on = [] { const char* v = std::getenv("ASSET_HIP_TUNING"); return v && std::atoi(v) != 0; }();
-  if (!on) {
-    // a knob that is set but not in effect: say so once, so that a measurement script which forgot the opt-in does not quote
-    // the default path under the knob's name
-    static bool warned = false;
-    if (!warned && std::getenv(name)) {
-      warned = true;
-      std::fprintf(stderr, "asset_hip: %s is set but IGNORED (dispatch knobs need ASSET_HIP_TUNING=1)\n", name);
-    }
-    return nullptr;
-  }
-  const char* v = std::getenv(name);
-  if (v) std::fprintf(stderr, "asset_hip: tuning knob %s=%s is in effect (ASSET_HIP_TUNING=1)\n", name, v);
-  return v;
+// ---- dispatch knobs of the measurement scripts (tools/README.md) -----------------------------------------------------------
+// Read ONCE, and only when the process opts in with ASSET_HIP_TUNING=1, so that a stray variable in a production environment
+// cannot change which kernels run.  With the opt-in, every knob that takes effect is reported on stderr; without it, a knob that
+// is set is reported as ignored, so that a measurement script which forgot the opt-in does not quote the default path under the
+// knob's name.  The planner takes a Tuning as an argument: Tuning() is the default dispatch whatever the environment holds.
+struct Tuning {
+  bool no_resident = false;   // ASSET_HIP_NO_RESIDENT: no resident kernel (nor its dense part behind the unit kernels)
+  bool skip_dense = false;    // ASSET_HIP_SKIP_DENSE: the ODE stage alone (times it; the outputs are not written)
+  bool no_alt_form = false;   // ASSET_HIP_NO_ALT_FORM: shapes with both dense forms (ResDims::RD_ALT) keep their tile form
+  bool no_affine = false;     // ASSET_HIP_NO_AFFINE: index tables are loaded even where their rows are runs (capi.hip)
+  int resident_grid = 0;      // ASSET_HIP_RESIDENT_GRID: waves of the resident kernel, level 2 (0: what the device holds)
+  int grid_b = 0;             // ASSET_HIP_GRID_B: workgroups of the dense stage (0: what the LDS lets be resident)
+  int alt_min = 5;            // ASSET_HIP_ALT_MIN: HALF segments per workgroup from which the one-group kernel takes the row-wise form
+  int lpair_min = 1;          // ASSET_HIP_LPAIR_MIN: groups per wave from which a looped mesh takes the pair form
+};
+inline const Tuning& tuning() {
+  static const Tuning tn = [] {
+    Tuning r;
+    const char* on = std::getenv("ASSET_HIP_TUNING");
+    const bool opted = on && std::atoi(on) != 0;
+    bool warned = false;
+    auto knob = [&](const char* name) -> const char* {
+      const char* v = std::getenv(name);
+      if (v && opted) std::fprintf(stderr, "asset_hip: tuning knob %s=%s is in effect (ASSET_HIP_TUNING=1)\n", name, v);
+      if (v && !opted && !warned) {
+        warned = true;
+        std::fprintf(stderr, "asset_hip: %s is set but IGNORED (dispatch knobs need ASSET_HIP_TUNING=1)\n", name);
+      }
+      return opted ? v : nullptr;
+    };
+    r.no_resident = knob("ASSET_HIP_NO_RESIDENT") != nullptr;
+    r.skip_dense = knob("ASSET_HIP_SKIP_DENSE") != nullptr;
+    r.no_alt_form = knob("ASSET_HIP_NO_ALT_FORM") != nullptr;
+    r.no_affine = knob("ASSET_HIP_NO_AFFINE") != nullptr;
+    if (const char* v = knob("ASSET_HIP_RESIDENT_GRID")) r.resident_grid = std::atoi(v);
+    if (const char* v = knob("ASSET_HIP_GRID_B")) r.grid_b = std::atoi(v);
+    if (const char* v = knob("ASSET_HIP_ALT_MIN")) r.alt_min = std::atoi(v);
+    if (const char* v = knob("ASSET_HIP_LPAIR_MIN")) r.lpair_min = std::atoi(v);
+    return r;
+  }();
+  return tn;
 }
-inline hipError_t launch_lgl_table(const KernelTable& t, int level, const EvalArgs& a, int cus, hipStream_t st) {
+
+// ---- the launch plan of one evaluation ------------------------------------------------------------------------------------------
+// plan_lgl decides (no HIP call, no environment, no allocation); launch_plan walks what it decided.
+struct PlanRequest {
+  int level;          // derivatives: 0 value, 1 + Jacobian, 2 + adjoint Hessian
+  bool blocks;        // KKT blocks are written
+  bool asmb;          // KKT entries are added straight into the solver's value array (EvalArgs::kmap)
+  bool adjgrad;       // the adjoint gradient is wanted and multipliers are given (AGX && L)
+  bool res_record;    // the handle holds the lane record of the resident kernel (EvalArgs::lane_consts_res)
+};
+enum PlanExtra { PLAN_NO_EXTRA = 0, PLAN_GP = 1, PLAN_WORK_RO = 2 };   // second kernel argument: none, segments per group, the workspace read-only
+struct PlanStep {
+  int slot;
+  unsigned grid_x, grid_y, block;
+  size_t lds_bytes;
+  int extra, gp;
+};
+struct LaunchPlan {
+  int nsteps = 0;
+  int units_gp = 0;   // EvalArgs::units_gp of the last step: the dense part follows the XCD placement of the unit stage
+  PlanStep step[3];
+};
+
+// ODE stage by units: segments per group so that the launch is about one workgroup per SIMD (groups x waves_per_seg ~ 4 per CU)
+inline int units_group(int nseg, int waves_per_seg, int cs, int cus) {
+  const int gp = int(((long long)nseg * waves_per_seg + 4 * cus - 1) / (4 * cus)), gpmax = 64 / cs;
+  return gp < 1 ? 1 : (gp > gpmax ? gpmax : gp);
+}
+// heavy ODEs, level 2: the one-launch unit stage while its workgroups are at most this many rounds of the device's SIMDs -- beyond
+// every mesh in practice, because it measured faster at every size tried (Betts-LGL5 x 1 000: 30.3 against 41.5 us, x 10 000:
+// 191.7 / 200.0; Betts-LGL7 x 5 000: 145.1 / 151.1); two launches (interior units, then cardinal units) beyond
+constexpr int kUnitsOneLaunchRounds = 1000;
+
+inline hipError_t plan_lgl(const KernelTable& t, const PlanRequest& rq, int nseg, int cus, const Tuning& tn, LaunchPlan& p) {
   const long long* m = t.meta;
-  const size_t bytes_ode = size_t(m[MF_BYTES_ODE]), bytes_dense = size_t(m[MF_BYTES_DENSE]);
-  const bool wide = m[MF_WIDE] != 0;
-  EvalArgs args = a;
-  void* kargs[] = {&args};
-  // ODE launch: the three ODE phases are latency chains, so spread the segments over every resident wave (fewest
-  // passes per wave); a workgroup walks its share in groups of at most G segments (= 64 points of the widest phase)
-  int per_cu_a = int((160 * 1024) / bytes_ode);
-  per_cu_a = per_cu_a < 1 ? 1 : (per_cu_a >= 8 ? 8 : (per_cu_a >= 4 ? 4 : per_cu_a));
-  const int grid_a = a.nseg < cus * per_cu_a ? a.nseg : cus * per_cu_a;
+  const int level = rq.level;
+  const bool asmb = rq.asmb;
+  p = LaunchPlan();
+  if (level < 0 || level > 2 || nseg < 1 || cus < 1) return hipErrorInvalidValue;
+  auto add = [&](int slot, long long gx, long long gy, int block, long long lds, int extra = PLAN_NO_EXTRA, int gp = 0) {
+    p.step[p.nsteps++] = PlanStep{slot, unsigned(gx), unsigned(gy), unsigned(block), size_t(lds), extra, gp};
+  };
+  auto by = [&](int l1, int l1a, int l2, int l2a) { return level == 2 ? (asmb ? l2a : l2) : (asmb ? l1a : l1); };
+  auto ceil_div = [](long long a, long long b) { return (a + b - 1) / b; };
+  auto least = [](long long a, long long b) { return a < b ? a : b; };
+
+  // value (evalOCC), and value + J^T lam without a Jacobian (evalRHS): one launch of the vector-Jacobian kernel, for the value
+  // without its gradient parts (a table without K_VALUE has no value-only kind: the launch reports the missing kernel)
+  if (level == 0 || (level == 1 && !rq.blocks && !asmb && rq.adjgrad && t.k[K_ADJGRAD])) {
+    add(level == 0 ? K_VALUE : K_ADJGRAD, ceil_div(nseg, m[MF_ADJ_GP]), 1, 64, m[MF_ADJ_LDS_BYTES]);
+    return hipSuccess;
+  }
+
+  // resident kernel (defect_resident.h): the ODE results stay in LDS.  One group per wave while a wave's share is at most GR
+  // segments, the looped instantiation beyond.
+  const int waves_dev = cus * 4 * int(m[MF_RES_WPS]);
+  if (m[MF_RES_GR] > 0 && !tn.no_resident && !tn.skip_dense && rq.res_record && t.k[by(K_RES1, K_RES1_ASM, K_RES2, K_RES2_ASM)] &&
+      (!asmb || m[MF_RES_ASM])) {
+    const int waves = (level == 2 && tn.resident_grid > 0) ? tn.resident_grid : waves_dev;
+    const long long share = ceil_div(nseg, waves);
+    const bool one = share <= m[MF_RES_GR];
+    const int kr = one ? by(K_RES1, K_RES1_ASM, K_RES2, K_RES2_ASM) : by(K_RESL1, K_RESL1_ASM, K_RESL2, K_RESL2_ASM);
+    if (t.k[kr]) {
+      // two-wave workgroups (a region of LDS each): the one-group kernel of a pair shape -- and, on every looped mesh, the looped
+      // level-2 block kernel of the shapes that are built with one (ResDims::LOOP_PAIR: row-wise dense part, a right-hand side
+      // heavy enough for the shared ODE stage to pay for the pair's barriers -- profiles/r6_forms2.txt)
+      const bool lpair = level == 2 && !one && !asmb && m[MF_RES_LOOP_NWV] > 1 && t.k[K_RESLP] && !(tn.no_alt_form && m[MF_RES_ALT]) &&
+                         share >= tn.lpair_min * m[MF_RES_GR];
+      const int nwv = ((one && m[MF_RES_NWV] > 1) || lpair) ? 2 : 1;
+      const long long nwg = ceil_div(least(nseg, waves), nwv);
+      // shapes with both forms of the dense part (ResDims::RD_ALT): rows in the one-group kernel from two and a half segments per
+      // workgroup on (with UNITC the row-wise part is the cheaper one wherever its passes -- four / two segments -- are not mostly
+      // empty: Reentry-LGL7 x 2 500 15.8 against 16.1 us, x 5 000 20.5 / 20.9, x 10 000 26.4 / 28.4; x 1 000 13.8 / 13.2), tiles below
+      const bool alt = level == 2 && one && nwv == 2 && !asmb && !tn.no_alt_form && m[MF_RES_ALT] && t.k[K_RES_ALT] &&
+                       2LL * nseg >= tn.alt_min * nwg;
+      add(lpair ? K_RESLP : (alt ? K_RES_ALT : kr), nwg, 1, 64 * nwv, m[MF_RES_LDS_BYTES] / (m[MF_RES_NWV] > 1 ? 2 : 1) * nwv);
+      return hipSuccess;
+    }
+  }
+
   // dense launch: persistent single-wave workgroups, as many as the LDS lets be resident
   // (an even number of waves per CU spreads evenly over the 4 SIMDs; 7 per CU measured 30% slower than 6)
-  int per_cu_b = int((160 * 1024) / bytes_dense);
-  per_cu_b = per_cu_b < 1 ? 1 : (per_cu_b >= 8 ? 8 : (per_cu_b >= 6 ? 6 : (per_cu_b >= 4 ? 4 : per_cu_b)));
-  int grid_b = a.nseg < cus * per_cu_b ? a.nseg : cus * per_cu_b;
-  const int wide_wgs = int(m[MF_WIDE_WGS]);   // four-wave workgroups per CU (defect_wide.h)
-  static const int env_b = tuning_env("ASSET_HIP_GRID_B") ? std::atoi(std::getenv("ASSET_HIP_GRID_B")) : 0;  // tuning only
-  if (env_b > 0) grid_b = env_b < a.nseg ? env_b : a.nseg;
-  static const bool skip_dense = tuning_env("ASSET_HIP_SKIP_DENSE") != nullptr;                               // tuning only
-  auto ode_stage = [&](int lv) { return klaunch(t.k[K_LGL(lv, 1, false)], dim3(grid_a), dim3(64), bytes_ode, st, kargs); };
-  // dense stage: single-wave workgroups, or (wide shapes, defect_wide.h) one four-wave workgroup per CU
-  auto dense_stage = [&](int lv) {
-    const bool asmb = a.kmap != nullptr;   // KKT entries added straight into the solver's value array
-    static const bool no_rows = tuning_env("ASSET_HIP_NO_ROWS") != nullptr;                                   // tuning only
+  const int fit_b = int((160 * 1024) / m[MF_BYTES_DENSE]);
+  const int per_cu_b = fit_b < 1 ? 1 : (fit_b >= 8 ? 8 : (fit_b >= 6 ? 6 : (fit_b >= 4 ? 4 : fit_b)));
+  const long long grid_b = least(nseg, tn.grid_b > 0 ? tn.grid_b : cus * per_cu_b);
+
+  if (m[MF_FUSED] && !tn.skip_dense) {
+    // STAGE 4: two-wave workgroups, the ODE bodies are issued once per pair of waves
+    // (measured, 10 000 segments: TwoBody-LGL5-BlockConstant 42.2 -> 39.6 us, Reentry-LGL7 43.2 -> 43.0 us; with 2-3 segments per
+    //  wave -- Reentry-LGL7 x 5 000 -- the pair's barriers cost more than the shared bodies save: 29.6 -> 32.9 us, so short shares
+    //  keep the one-wave form)
+    const long long pairs = grid_b / 2, share2 = pairs > 0 ? ceil_div(nseg, 2 * pairs) : 0;
+    if (level == 2 && m[MF_FUSED2] && !asmb && pairs > 0 && share2 >= 4 && share2 <= m[MF_GF2] / 2) {
+      add(K_LGL2_S4, pairs, 1, 128, m[MF_BYTES_FUSED2]);
+      return hipSuccess;
+    }
+    // STAGE 3: a single launch when every workgroup's share fits one group of the fused kernel (also with on-device assembly: the
+    // dense part places its entries through the map either way)
+    const int k3 = by(K_LGL1_S3, K_LGL1_S3_ASM, K_LGL2_S3, K_LGL2_S3_ASM);
+    if (ceil_div(nseg, grid_b) <= m[MF_GF] && t.k[k3]) {
+      add(k3, grid_b, 1, 64, m[MF_BYTES_DENSE]);
+      return hipSuccess;
+    }
+  }
+
+  // ---- two stages: the ODE results go through the workspace
+  const int nunits = int(m[MF_NUNITS]), cs = int(m[MF_CS]);
+  int xcd_gp = 0;   // segments per group of a unit stage placed by XCD (below)
+  if (nunits > 1 && level == 1 && t.k[K_UNITSJ] && (long long)nseg * cs <= 64LL * cus) {
+    // heavy right-hand side, Jacobian kinds: one wave per output unit (defect_units.h, PHASE 3) -- while the mesh leaves SIMDs
+    // idle: the units recompute what they share, and from ~16 cardinal points per SIMD on the one-body-per-lane stage is the
+    // faster one (Betts-LGL5: 1 000 segments 21.5 against 48.1 us, 5 000: 48.8 / 53.8, 10 000: 85.0 / 72.7)
+    const int gp = units_group(nseg, nunits, cs, cus);
+    add(K_UNITSJ, ceil_div(nseg, gp), nunits, 64, m[MF_UNITS_BASE_BYTES] + gp * m[MF_UNITS_SLOT_BYTES], PLAN_GP, gp);
+  } else if (nunits > 1 && level == 2) {
+    // One launch (PHASE 4: every cardinal unit forms the interior gradients it needs itself, so 2 x units waves per segment)
+    const int gp4 = units_group(nseg, 2 * nunits, cs, cus);
+    const long long ng4 = ceil_div(nseg, gp4);
+    if (t.k[K_UNITS4] && ng4 * 2 * nunits <= (long long)kUnitsOneLaunchRounds * 4 * cus) {
+      // XCD-aware placement (MI355X: 8 XCDs; on a part with another count the mapping below is still a valid split of the work --
+      // it only stops coinciding with the L2s): workgroups go to the eight XCDs round robin in launch order (x fastest), so with
+      // the number of groups padded to a multiple of eight every unit of group g runs on XCD g % 8 -- its slot is assembled in ONE
+      // L2 (no 32-byte sector written back half-filled by several of them) -- and the dense part reads it there
+      add(K_UNITS4, (ng4 + 7) & ~7LL, 2 * nunits, 64, m[MF_UNITS_BASE_BYTES] + gp4 * m[MF_UNITS_SLOT_BYTES], PLAN_GP, gp4);
+      // (the dense part follows only while its shares stay as even as the plain split's -- every group is divided among a whole
+      //  number of waves: Betts-LGL5 x 1 000: 29.9 -> 28.6 us; x 2 000, where that leaves 3 segments to some waves and 2 to others:
+      //  51.3 -> 55.7 us.  The padded unit grid alone: Betts-LGL5 x 5 000 106.7 -> 101.2 us, Betts-LGL7 x 5 000 145.4 -> 138.0 us)
+      const long long gx = (ng4 + 7) / 8, wpg = gx > 0 ? (waves_dev / 8) / gx : 0;
+      if (waves_dev % 8 == 0 && wpg > 0 && ceil_div(gp4, wpg) <= ceil_div(nseg, waves_dev)) xcd_gp = gp4;
+    } else {
+      const int gp = units_group(nseg, nunits, cs, cus);
+      const long long bytes = m[MF_UNITS_BASE_BYTES] + gp * m[MF_UNITS_SLOT_BYTES];
+      add(K_UNITS0, ceil_div(nseg, gp), nunits, 64, bytes, PLAN_GP, gp);
+      add(K_UNITS1, ceil_div(nseg, gp), nunits, 64, bytes, PLAN_GP, gp);
+    }
+  } else {
+    // the three ODE phases are latency chains, so spread the segments over every resident wave (fewest passes per wave); a
+    // workgroup walks its share in groups of at most G segments (= 64 points of the widest phase)
+    const int fit_a = int((160 * 1024) / m[MF_BYTES_ODE]);
+    const int per_cu_a = fit_a < 1 ? 1 : (fit_a >= 8 ? 8 : (fit_a >= 4 ? 4 : fit_a));
+    add(level == 2 ? K_LGL2_S1 : K_LGL1_S1, least(nseg, cus * per_cu_a), 1, 64, m[MF_BYTES_ODE]);
+  }
+  if (tn.skip_dense) return hipSuccess;
+  p.units_gp = xcd_gp;
+
+  if (level == 2 && m[MF_RESD_GR] > 0 && !tn.no_resident && rq.res_record && t.k[asmb ? K_RESD_ASM : K_RESD]) {
+    // dense part of the resident kernel over the slots the units wrote (XCD-aware placement: the whole grid, a wave's segments
+    // follow from its XCD; otherwise a wave per segment at most)
+    add(asmb ? K_RESD_ASM : K_RESD, xcd_gp > 0 ? waves_dev : least(nseg, waves_dev), 1, 64, m[MF_RES_LDS_BYTES]);
+  } else if (m[MF_WIDE] && !asmb && m[MF_ROWS_LDS_BYTES] > 0 && cs >= 3 && t.k[level == 2 ? K_ROWS2 : K_ROWS1]) {
     // (LGL3: two nodes, IR = 2 q -- one of the two H blocks nearly empty: 487 against 399 us for 12 500 32-state segments; kept
     //  with the tile kernel)
-    if (wide && lv >= 1 && !asmb && !no_rows && m[MF_ROWS_LDS_BYTES] > 0 && m[MF_CS] >= 3 && t.k[lv == 2 ? K_ROWS : K_ROWS1]) {
-      const double* work_ro = a.work;
-      void* rargs[] = {&args, &work_ro};
-      return klaunch(t.k[lv == 2 ? K_ROWS : K_ROWS1], dim3(a.nseg < cus ? a.nseg : cus), dim3(256), size_t(m[MF_ROWS_LDS_BYTES]), st, rargs);
-    }
-    if (wide)
-      return klaunch(t.k[K_WIDE(lv, asmb)], dim3(a.nseg < cus * wide_wgs ? a.nseg : cus * wide_wgs), dim3(256), bytes_dense, st, kargs);
-    return klaunch(t.k[K_LGL(lv, 2, asmb)], dim3(grid_b), dim3(64), bytes_dense, st, kargs);
-  };
-  hipError_t e;
-  // constraints_adjointgradient (evalRHS): value and J^T lam wanted, no Jacobian -- one launch of the vector-Jacobian kernel
-  static const bool no_adj = tuning_env("ASSET_HIP_NO_ADJGRAD_KERNEL") != nullptr;                            // tuning only
-  if (level == 1 && !a.KKT && !a.kmap && a.AGX && a.L && !no_adj && t.k[K_ADJGRAD]) {
-    const int gp = int(m[MF_ADJ_GP]);
-    return klaunch(t.k[K_ADJGRAD], dim3((a.nseg + gp - 1) / gp), dim3(64), size_t(m[MF_ADJ_LDS_BYTES]), st, kargs);
+    add(level == 2 ? K_ROWS2 : K_ROWS1, least(nseg, cus), 1, 256, m[MF_ROWS_LDS_BYTES], PLAN_WORK_RO);
+  } else if (m[MF_WIDE]) {   // one four-wave workgroup per CU, or MF_WIDE_WGS of them (defect_wide.h)
+    add(by(K_WIDE1, K_WIDE1_ASM, K_WIDE2, K_WIDE2_ASM), least(nseg, cus * m[MF_WIDE_WGS]), 1, 256, m[MF_BYTES_DENSE]);
+  } else {
+    add(by(K_LGL1_S2, K_LGL1_S2_ASM, K_LGL2_S2, K_LGL2_S2_ASM), grid_b, 1, 64, m[MF_BYTES_DENSE]);
   }
-  if (level == 0 && !no_adj && t.k[K_VALUE]) {   // constraints (evalOCC): the same kernel without its gradient parts
-    const int gp = int(m[MF_ADJ_GP]);
-    return klaunch(t.k[K_VALUE], dim3((a.nseg + gp - 1) / gp), dim3(64), size_t(m[MF_ADJ_LDS_BYTES]), st, kargs);
+  return hipSuccess;
+}
+
+inline hipError_t launch_plan(const KernelTable& t, const LaunchPlan& p, const EvalArgs& a, hipStream_t st) {
+  EvalArgs args = a;
+  for (int i = 0; i < p.nsteps; i++) {
+    const PlanStep& s = p.step[i];
+    if (i + 1 == p.nsteps && p.units_gp > 0) args.units_gp = p.units_gp;
+    int gp = s.gp;
+    const double* work_ro = a.work;
+    void* kargs[] = {&args, s.extra == PLAN_GP ? static_cast<void*>(&gp) : static_cast<void*>(&work_ro)};   // (one-argument kernels read the first only)
+    const hipError_t e = klaunch(t.k[s.slot], dim3(s.grid_x, s.grid_y), dim3(s.block), s.lds_bytes, st, kargs);
+    if (e != hipSuccess) return e;
   }
-  switch (level) {
-    case 0: return ode_stage(0);
-    case 1: {
-      static const bool no_res1 = tuning_env("ASSET_HIP_NO_RESIDENT") != nullptr;                             // tuning only
-      if (m[MF_RES_GR] > 0 && !no_res1 && !skip_dense && a.lane_consts_res && t.k[K_RES1(a.kmap != nullptr)] && (!a.kmap || m[MF_RES_ASM])) {
-        const int waves = cus * 4 * int(m[MF_RES_WPS]);   // resident kernel, Jacobian kinds (defect_resident.h, LEVEL 1)
-        const bool one = (a.nseg + waves - 1) / waves <= int(m[MF_RES_GR]);
-        const KRef& kr = one ? t.k[K_RES1(a.kmap != nullptr)] : t.k[K_RESL(1, a.kmap != nullptr)];
-        // (the one-group kernel of a pair shape: two waves per workgroup, a region of LDS each; the looped one: single waves)
-        const int nwv = (one && m[MF_RES_NWV] > 1) ? 2 : 1, nw = a.nseg < waves ? a.nseg : waves;
-        const size_t lds = size_t(m[MF_RES_LDS_BYTES]) / size_t(m[MF_RES_NWV] > 1 ? 2 : 1) * size_t(nwv);
-        if (kr) return klaunch(kr, dim3((nw + nwv - 1) / nwv), dim3(64 * nwv), lds, st, kargs);
-      }
-      static const bool no_fuse1 = tuning_env("ASSET_HIP_NO_FUSE") != nullptr;                                // tuning only
-      if (m[MF_FUSED] && !no_fuse1 && !skip_dense && (a.nseg + grid_b - 1) / grid_b <= int(m[MF_GF]) && t.k[K_LGL(1, 3, a.kmap != nullptr)])
-        return klaunch(t.k[K_LGL(1, 3, a.kmap != nullptr)], dim3(grid_b), dim3(64), bytes_dense, st, kargs);   // one launch
-      static const bool no_units1 = tuning_env("ASSET_HIP_NO_UNITS") != nullptr;                              // tuning only
-      if (m[MF_NUNITS] > 1 && !no_units1 && t.k[K_UNITSJ] && a.nseg * int(m[MF_CS]) <= 64 * cus) {
-        // heavy right-hand side: one wave per output unit (defect_units.h, PHASE 3), one launch -- while the mesh leaves SIMDs
-        // idle: the units recompute what they share, and from ~16 cardinal points per SIMD on the one-body-per-lane stage
-        // is the faster one (Betts-LGL5: 1 000 segments 21.5 against 48.1 us, 5 000: 48.8 / 53.8, 10 000: 85.0 / 72.7)
-        const int nunits = int(m[MF_NUNITS]), gpmax = 64 / int(m[MF_CS]);
-        int gp = (a.nseg * nunits + 4 * cus - 1) / (4 * cus);
-        gp = gp < 1 ? 1 : (gp > gpmax ? gpmax : gp);
-        const size_t bytes_units = size_t(m[MF_UNITS_BASE_BYTES]) + size_t(gp) * size_t(m[MF_UNITS_SLOT_BYTES]);
-        void* uargs[] = {&args, &gp};
-        if ((e = klaunch(t.k[K_UNITSJ], dim3((a.nseg + gp - 1) / gp, nunits), dim3(64), bytes_units, st, uargs)) != hipSuccess) return e;
-      } else if ((e = ode_stage(1)) != hipSuccess) {
-        return e;
-      }
-      if (skip_dense) return hipSuccess;
-      return dense_stage(1);
-    }
-    case 2: {
-      // resident kernel (defect_resident.h): the ODE results stay in LDS; meshes of at most GR segments per wave
-      static const bool no_res = tuning_env("ASSET_HIP_NO_RESIDENT") != nullptr;                              // tuning only
-      if (m[MF_RES_GR] > 0 && !no_res && !skip_dense && a.lane_consts_res && t.k[K_RES(a.kmap != nullptr)] && (!a.kmap || m[MF_RES_ASM])) {
-        int waves = cus * 4 * int(m[MF_RES_WPS]);   // one group per wave up to GR segments per wave, the looped instantiation beyond
-        static const int env_max = tuning_env("ASSET_HIP_RESIDENT_MAX_GROUPS") ? std::atoi(std::getenv("ASSET_HIP_RESIDENT_MAX_GROUPS")) : 0;   // tuning only
-        static const int env_grid = tuning_env("ASSET_HIP_RESIDENT_GRID") ? std::atoi(std::getenv("ASSET_HIP_RESIDENT_GRID")) : 0;   // tuning only
-        if (env_grid > 0) waves = env_grid;
-        const bool one = (a.nseg + waves - 1) / waves <= int(m[MF_RES_GR]);
-        const KRef& kr = one ? t.k[K_RES(a.kmap != nullptr)] : t.k[K_RESL(2, a.kmap != nullptr)];
-        if (kr && (one || env_max <= 0 || (a.nseg + waves - 1) / waves <= env_max * int(m[MF_RES_GR])))
-        {
-          // two-wave workgroups: the one-group kernel of a pair shape -- and, on every looped mesh, the looped block kernel of the shapes
-          // that are built with one (ResDims::LOOP_PAIR: row-wise dense part, a right-hand side heavy enough for the shared ODE stage to
-          // pay for the pair's barriers -- profiles/r6_forms2.txt)
-          static const bool no_alt = tuning_env("ASSET_HIP_NO_ALT_FORM") != nullptr;                           // tuning only
-          static const int lpair_min = tuning_env("ASSET_HIP_LPAIR_MIN") ? std::atoi(std::getenv("ASSET_HIP_LPAIR_MIN")) : 1;   // tuning only (groups per wave from which the pair form is taken)
-          static const int alt_min = tuning_env("ASSET_HIP_ALT_MIN") ? std::atoi(std::getenv("ASSET_HIP_ALT_MIN")) : 5;         // tuning only (HALF segments per workgroup)
-          const bool lpair = !one && !a.kmap && m[MF_RES_LOOP_NWV] > 1 && t.k[K_RESLP] && !(no_alt && m[MF_RES_ALT]) &&
-                             (a.nseg + waves - 1) / waves >= lpair_min * int(m[MF_RES_GR]);
-          const int nwv = ((one && m[MF_RES_NWV] > 1) || lpair) ? 2 : 1, nw = a.nseg < waves ? a.nseg : waves;
-          const size_t lds = size_t(m[MF_RES_LDS_BYTES]) / size_t(m[MF_RES_NWV] > 1 ? 2 : 1) * size_t(nwv);
-          // shapes with both forms of the dense part (ResDims::RD_ALT): rows in the one-group kernel from two and a half segments per
-          // workgroup on (with UNITC the row-wise part is the cheaper one wherever its passes -- four / two segments -- are not mostly
-          // empty: Reentry-LGL7 x 2 500 15.8 against 16.1 us, x 5 000 20.5 / 20.9, x 10 000 26.4 / 28.4; x 1 000 13.8 / 13.2), tiles below;
-          // looped meshes: the looped pair kernel (rows) -- profiles/r6_forms2.txt
-          const int nwg = (nw + nwv - 1) / nwv;
-          const bool alt = one && nwv == 2 && !a.kmap && !no_alt && m[MF_RES_ALT] && t.k[K_RES_ALT] && 2 * a.nseg >= alt_min * nwg;
-          return klaunch(lpair ? t.k[K_RESLP] : (alt ? t.k[K_RES_ALT] : kr), dim3(nwg), dim3(64 * nwv), lds, st, kargs);
-        }
-      }
-      if (m[MF_FUSED]) {
-        // single launch when every workgroup's share fits one group of the fused kernel (defect_kernels.h, STAGE 3)
-        static const bool no_fuse = tuning_env("ASSET_HIP_NO_FUSE") != nullptr;                               // tuning only
-        if (m[MF_FUSED2]) {
-          // two-wave workgroups: the ODE bodies are issued once per pair of waves (defect_kernels.h, STAGE 4)
-          static const bool no_fuse2 = tuning_env("ASSET_HIP_NO_FUSE2") != nullptr;                           // tuning only
-          const int pairs = grid_b / 2;
-          // (measured, 10 000 segments: TwoBody-LGL5-BlockConstant 42.2 -> 39.6 us, Reentry-LGL7 43.2 -> 43.0 us; with 2-3
-          //  segments per wave -- Reentry-LGL7 x 5 000 -- the pair's barriers cost more than the shared bodies save:
-          //  29.6 -> 32.9 us, so short shares keep the one-wave form)
-          const int share = (a.nseg + 2 * pairs - 1) / (pairs > 0 ? 2 * pairs : 1);
-          if (!a.kmap && !no_fuse && !no_fuse2 && !skip_dense && pairs > 0 && share >= 4 && share <= int(m[MF_GF2]) / 2)
-            return klaunch(t.k[K_LGL(2, 4, false)], dim3(pairs), dim3(128), size_t(m[MF_BYTES_FUSED2]), st, kargs);
-        }
-        // (also with on-device assembly: the dense part places its entries through the map either way)
-        if (!no_fuse && !skip_dense && (a.nseg + grid_b - 1) / grid_b <= int(m[MF_GF]))
-          return klaunch(t.k[K_LGL(2, 3, a.kmap != nullptr)], dim3(grid_b), dim3(64), bytes_dense, st, kargs);
-      }
-      static const bool no_units = tuning_env("ASSET_HIP_NO_UNITS") != nullptr;                               // tuning only
-      if (m[MF_NUNITS] > 1 && !no_units) {
-        // heavy right-hand side: the ODE stage runs one wave per output unit (defect_units.h)
-        const int nunits = int(m[MF_NUNITS]), gpmax = 64 / int(m[MF_CS]);
-        // about one workgroup per SIMD: groups x units ~ 4 per CU
-        int gp = (a.nseg * nunits + 4 * cus - 1) / (4 * cus);
-        gp = gp < 1 ? 1 : (gp > gpmax ? gpmax : gp);
-        const size_t bytes_units = size_t(m[MF_UNITS_BASE_BYTES]) + size_t(gp) * size_t(m[MF_UNITS_SLOT_BYTES]);
-        // One launch (PHASE 4: every cardinal unit forms the interior gradients it needs itself) while its 2 x units x groups
-        // workgroups are about one round of the device's SIMDs; two launches (interior units, then cardinal units) beyond
-        static const int units1 = tuning_env("ASSET_HIP_UNITS_ONE_LAUNCH") ? std::atoi(std::getenv("ASSET_HIP_UNITS_ONE_LAUNCH")) : -1;   // tuning only
-        int gp4 = (a.nseg * 2 * nunits + 4 * cus - 1) / (4 * cus);
-        gp4 = gp4 < 1 ? 1 : (gp4 > gpmax ? gpmax : gp4);
-        const long long wgs4 = (long long)((a.nseg + gp4 - 1) / gp4) * 2 * nunits;
-        const bool one_launch = t.k[K_UNITS4] && (units1 >= 0 ? units1 != 0 : wgs4 <= (long long)(ASSET_UNITS_ONE_LAUNCH_ROUNDS * 4) * cus);
-        if (one_launch) {
-          // XCD-aware placement (MI355X: 8 XCDs; on a part with another count the mapping below is still a valid split of the work --
-          // it only stops coinciding with the L2s): workgroups go to the eight XCDs round robin in launch order (x fastest), so with the number of
-          // groups padded to a multiple of eight every unit of group g runs on XCD g % 8 -- its slot is assembled in ONE L2 (no
-          // 32-byte sector written back half-filled by several of them) -- and the dense part reads it there (units_gp below)
-          const size_t bytes4 = size_t(m[MF_UNITS_BASE_BYTES]) + size_t(gp4) * size_t(m[MF_UNITS_SLOT_BYTES]);
-          void* uargs4[] = {&args, &gp4};
-          const int ng4 = (a.nseg + gp4 - 1) / gp4, ng4p = (ng4 + 7) & ~7;
-          if ((e = klaunch(t.k[K_UNITS4], dim3(ng4p, 2 * nunits), dim3(64), bytes4, st, uargs4)) != hipSuccess) return e;
-          static const bool no_xcd = tuning_env("ASSET_HIP_NO_XCD_PLACEMENT") != nullptr;                       // tuning only
-          // (the dense part follows only while its shares stay as even as the plain split's -- every group is divided among a whole
-          //  number of waves: Betts-LGL5 x 1 000: 29.9 -> 28.6 us; x 2 000, where that leaves 3 segments to some waves and 2 to others:
-          //  51.3 -> 55.7 us.  The padded unit grid alone: Betts-LGL5 x 5 000 106.7 -> 101.2 us, Betts-LGL7 x 5 000 145.4 -> 138.0 us)
-          const int dwaves = cus * 4 * int(m[MF_RES_WPS]), gx = (ng4 + 7) / 8, wpg = gx > 0 ? (dwaves / 8) / gx : 0;
-          if (!no_xcd && dwaves % 8 == 0 && wpg > 0 && (gp4 + wpg - 1) / wpg <= (a.nseg + dwaves - 1) / dwaves) args.units_gp = gp4;
-        } else {
-        const dim3 grid((a.nseg + gp - 1) / gp, nunits);
-        void* uargs[] = {&args, &gp};
-        if ((e = klaunch(t.k[K_UNITS0], grid, dim3(64), bytes_units, st, uargs)) != hipSuccess) return e;
-        if ((e = klaunch(t.k[K_UNITS1], grid, dim3(64), bytes_units, st, uargs)) != hipSuccess) return e;
-        }
-      } else if ((e = ode_stage(2)) != hipSuccess) {
-        return e;
-      }
-      if (skip_dense) return hipSuccess;
-      static const bool no_resd = tuning_env("ASSET_HIP_NO_RESIDENT") != nullptr;                             // tuning only
-      if (m[MF_RESD_GR] > 0 && !no_resd && a.lane_consts_res && t.k[K_RESD(a.kmap != nullptr)]) {
-        const int waves = cus * 4 * int(m[MF_RES_WPS]);   // dense part of the resident kernel over the slots the units wrote
-        // (XCD-aware placement: the whole grid, a wave's segments follow from its XCD; otherwise a wave per segment at most)
-        const int nwg = args.units_gp > 0 ? waves : (a.nseg < waves ? a.nseg : waves);
-        return klaunch(t.k[K_RESD(a.kmap != nullptr)], dim3(nwg), dim3(64), size_t(m[MF_RES_LDS_BYTES]), st, kargs);
-      }
-      return dense_stage(2);
-    }
-  }
-  return hipErrorInvalidValue;
+  return hipSuccess;
+}
+inline PlanRequest plan_request(int level, const EvalArgs& a) {
+  return PlanRequest{level, a.KKT != nullptr, a.kmap != nullptr, a.AGX && a.L, a.lane_consts_res != nullptr};
 }
 
 // A plain function batched over applications: transcription id 0 (func_kernels.h)
@@ -406,11 +479,15 @@ inline hipError_t launch_func_table(const KernelTable& t, int level, const EvalA
   const bool staged = level >= 1 && !asmb && t.meta[MF_G] > 0;
   const int apw = staged ? int(t.meta[MF_G]) : 64;
   const size_t shmem = staged ? size_t(t.meta[MF_LDS_BYTES]) : 0;
-  return klaunch(t.k[K_FUNC(level, asmb)], dim3((a.nseg + apw - 1) / apw), dim3(64), shmem, st, kargs);
+  const int slot = level == 0 ? K_FUNC0 : (level == 1 ? (asmb ? K_FUNC1_ASM : K_FUNC1) : (asmb ? K_FUNC2_ASM : K_FUNC2));
+  return klaunch(t.k[slot], dim3((a.nseg + apw - 1) / apw), dim3(64), shmem, st, kargs);
 }
 
 inline hipError_t entry_launch(const KernelEntry* ke, int level, const EvalArgs& a, int cus, hipStream_t st) {
-  return ke->table->meta[MF_KIND] == 2 ? launch_func_table(*ke->table, level, a, st) : launch_lgl_table(*ke->table, level, a, cus, st);
+  if (ke->table->meta[MF_KIND] == 2) return launch_func_table(*ke->table, level, a, st);
+  LaunchPlan p;
+  const hipError_t e = plan_lgl(*ke->table, plan_request(level, a), a.nseg, cus, tuning(), p);
+  return e != hipSuccess ? e : launch_plan(*ke->table, p, a, st);
 }
 
 // de Boor mesh-error estimate (mesh_kernels.h); only transcriptions of an ODE have it
@@ -462,88 +539,47 @@ inline hipError_t entry_lane_setup(const KernelEntry* ke, int level, void* out, 
 
 // ---- tables of the kernels linked into this translation unit ---------------------------------------------------------
 #define ASSET_KPTR(...) reinterpret_cast<const void*>(&__VA_ARGS__)
+#define ASSET_FILL_LGLG(NAME, COND, T, ...) if constexpr (COND) r.k[NAME].host = ASSET_KPTR(T<Ode, SCH, BLOCKED, G, ##__VA_ARGS__>);
+#define ASSET_FILL_LGL(NAME, COND, T, ...) if constexpr (COND) r.k[NAME].host = ASSET_KPTR(T<Ode, SCH, BLOCKED, ##__VA_ARGS__>);
+#define ASSET_FILL_NONE(NAME, COND, T, ...) if constexpr (COND) r.k[NAME].host = ASSET_KPTR(T<__VA_ARGS__>);
+#define ASSET_FILL_FUNC(NAME, COND, T, ...)
+#define ASSET_FILL_BUNDLE(NAME, COND, T, ...)
+#define ASSET_X_FILL(NAME, FAMILY, COND, T, ...) ASSET_FILL_##FAMILY(NAME, COND, T, ##__VA_ARGS__)
 template <class Ode, int SCH, bool BLOCKED, int G>
 const KernelTable* lgl_static_table() {
   using D = Dims<Ode, SCH, BLOCKED>;
   static KernelTable t = [] {
     KernelTable r;
     for (int i = 0; i < MF_COUNT; i++) r.meta[i] = LglMeta<Ode, SCH, BLOCKED, G>::v[i];
-    r.k[K_LGL(0, 1, false)].host = ASSET_KPTR(lgl_defect_kernel<Ode, SCH, BLOCKED, G, 0, 1, false>);
-    r.k[K_LGL(1, 1, false)].host = ASSET_KPTR(lgl_defect_kernel<Ode, SCH, BLOCKED, G, 1, 1, false>);
-    r.k[K_LGL(2, 1, false)].host = ASSET_KPTR(lgl_defect_kernel<Ode, SCH, BLOCKED, G, 2, 1, false>);
-    if constexpr (D::WIDE) {
-      r.k[K_WIDE(1, false)].host = ASSET_KPTR(lgl_wide_dense_kernel<Ode, SCH, BLOCKED, 1, false>);
-      r.k[K_WIDE(1, true)].host = ASSET_KPTR(lgl_wide_dense_kernel<Ode, SCH, BLOCKED, 1, true>);
-      r.k[K_WIDE(2, false)].host = ASSET_KPTR(lgl_wide_dense_kernel<Ode, SCH, BLOCKED, 2, false>);
-      r.k[K_WIDE(2, true)].host = ASSET_KPTR(lgl_wide_dense_kernel<Ode, SCH, BLOCKED, 2, true>);
-      r.k[K_WIDE_SETUP].host = ASSET_KPTR(wide_setup_kernel<Ode, SCH, BLOCKED>);
-      if constexpr (RowsDims<D>::OK) {
-        r.k[K_ROWS].host = ASSET_KPTR(lgl_rows_kernel<Ode, SCH, BLOCKED, 2>);
-        r.k[K_ROWS1].host = ASSET_KPTR(lgl_rows_kernel<Ode, SCH, BLOCKED, 1>);
-      }
-    } else {
-      r.k[K_LGL(1, 2, false)].host = ASSET_KPTR(lgl_defect_kernel<Ode, SCH, BLOCKED, G, 1, 2, false>);
-      r.k[K_LGL(1, 2, true)].host = ASSET_KPTR(lgl_defect_kernel<Ode, SCH, BLOCKED, G, 1, 2, true>);
-      r.k[K_LGL(2, 2, false)].host = ASSET_KPTR(lgl_defect_kernel<Ode, SCH, BLOCKED, G, 2, 2, false>);
-      r.k[K_LGL(2, 2, true)].host = ASSET_KPTR(lgl_defect_kernel<Ode, SCH, BLOCKED, G, 2, 2, true>);
-      r.k[K_LANE_SETUP1].host = ASSET_KPTR(lane_setup_kernel<Ode, SCH, BLOCKED, 1>);
-      r.k[K_LANE_SETUP2].host = ASSET_KPTR(lane_setup_kernel<Ode, SCH, BLOCKED, 2>);
-      if constexpr (D::FUSED) {
-        r.k[K_LGL(2, 3, false)].host = ASSET_KPTR(lgl_defect_kernel<Ode, SCH, BLOCKED, G, 2, 3, false>);
-        r.k[K_LGL(2, 3, true)].host = ASSET_KPTR(lgl_defect_kernel<Ode, SCH, BLOCKED, G, 2, 3, true>);
-        r.k[K_LGL(1, 3, false)].host = ASSET_KPTR(lgl_defect_kernel<Ode, SCH, BLOCKED, G, 1, 3, false>);
-        r.k[K_LGL(1, 3, true)].host = ASSET_KPTR(lgl_defect_kernel<Ode, SCH, BLOCKED, G, 1, 3, true>);
-      }
-      if constexpr (D::FUSED2) r.k[K_LGL(2, 4, false)].host = ASSET_KPTR(lgl_defect_kernel<Ode, SCH, BLOCKED, G, 2, 4, false>);
-      if constexpr (ResDims<D>::OK) {
-        r.k[K_RES(false)].host = ASSET_KPTR(lgl_resident_kernel<Ode, SCH, BLOCKED, 2, false>);
-        r.k[K_RES(true)].host = ASSET_KPTR(lgl_resident_kernel<Ode, SCH, BLOCKED, 2, true>);
-        r.k[K_RES1(false)].host = ASSET_KPTR(lgl_resident_kernel<Ode, SCH, BLOCKED, 1, false>);
-        r.k[K_RES1(true)].host = ASSET_KPTR(lgl_resident_kernel<Ode, SCH, BLOCKED, 1, true>);
-        r.k[K_RESL(2, false)].host = ASSET_KPTR(lgl_resident_kernel<Ode, SCH, BLOCKED, 2, false, true>);
-        r.k[K_RESL(2, true)].host = ASSET_KPTR(lgl_resident_kernel<Ode, SCH, BLOCKED, 2, true, true>);
-        r.k[K_RESL(1, false)].host = ASSET_KPTR(lgl_resident_kernel<Ode, SCH, BLOCKED, 1, false, true>);
-        r.k[K_RESL(1, true)].host = ASSET_KPTR(lgl_resident_kernel<Ode, SCH, BLOCKED, 1, true, true>);
-        r.k[K_RES_SETUP].host = ASSET_KPTR(res_lane_setup_kernel<Ode, SCH, BLOCKED>);
-        if constexpr (ResDims<D>::LOOP_PAIR) r.k[K_RESLP].host = ASSET_KPTR(lgl_resident_kernel<Ode, SCH, BLOCKED, 2, false, true, false, true>);
-        if constexpr (ResDims<D>::RD_ALT) r.k[K_RES_ALT].host = ASSET_KPTR(lgl_resident_kernel<Ode, SCH, BLOCKED, 2, false, false, false, false, 1>);
-      }
-      if constexpr (ResDims<D>::GIVEN_OK) {
-        r.k[K_RESD(false)].host = ASSET_KPTR(lgl_resident_kernel<Ode, SCH, BLOCKED, 2, false, true, true>);
-        r.k[K_RESD(true)].host = ASSET_KPTR(lgl_resident_kernel<Ode, SCH, BLOCKED, 2, true, true, true>);
-        r.k[K_RES_SETUP].host = ASSET_KPTR(res_lane_setup_kernel<Ode, SCH, BLOCKED>);
-      }
-    }
-    if constexpr (Ode::NUNITS > 1) {
-      r.k[K_UNITS0].host = ASSET_KPTR(lgl_ode_units_kernel<Ode, SCH, BLOCKED, 0>);
-      r.k[K_UNITS1].host = ASSET_KPTR(lgl_ode_units_kernel<Ode, SCH, BLOCKED, 1>);
-      r.k[K_UNITSJ].host = ASSET_KPTR(lgl_ode_units_kernel<Ode, SCH, BLOCKED, 3>);
-      r.k[K_UNITS4].host = ASSET_KPTR(lgl_ode_units_kernel<Ode, SCH, BLOCKED, 4>);
-    }
-    r.k[K_ADJGRAD].host = ASSET_KPTR(lgl_adjgrad_kernel<Ode, SCH, BLOCKED, true>);
-    r.k[K_VALUE].host = ASSET_KPTR(lgl_adjgrad_kernel<Ode, SCH, BLOCKED, false>);
-    r.k[K_MESH_YVEC].host = ASSET_KPTR(mesh_yvec_kernel<Ode, SCH, BLOCKED>);
-    r.k[K_MESH_ERROR].host = ASSET_KPTR(mesh_error_kernel<0>);
-    r.k[K_INTERP_XDOT].host = ASSET_KPTR(interp_xdot_kernel<Ode, SCH, BLOCKED>);
-    r.k[K_INTERP_EVAL].host = ASSET_KPTR(interp_eval_kernel<Ode, SCH, BLOCKED>);
+    ASSET_KERNELS(ASSET_X_FILL)
     return r;
   }();
   return &t;
 }
+#undef ASSET_FILL_LGLG
+#undef ASSET_FILL_LGL
+#undef ASSET_FILL_NONE
+#undef ASSET_FILL_FUNC
+#define ASSET_FILL_LGLG(NAME, COND, T, ...)
+#define ASSET_FILL_LGL(NAME, COND, T, ...)
+#define ASSET_FILL_NONE(NAME, COND, T, ...)
+#define ASSET_FILL_FUNC(NAME, COND, T, ...) r.k[NAME].host = ASSET_KPTR(T<F, ##__VA_ARGS__>);
 template <class F>
 const KernelTable* func_static_table() {
   static KernelTable t = [] {
     KernelTable r;
     for (int i = 0; i < MF_COUNT; i++) r.meta[i] = FuncMeta<F>::v[i];
-    r.k[K_FUNC(0, false)].host = ASSET_KPTR(func_kernel<F, 0, false>);
-    r.k[K_FUNC(1, false)].host = ASSET_KPTR(func_kernel<F, 1, false>);
-    r.k[K_FUNC(1, true)].host = ASSET_KPTR(func_kernel<F, 1, true>);
-    r.k[K_FUNC(2, false)].host = ASSET_KPTR(func_kernel<F, 2, false>);
-    r.k[K_FUNC(2, true)].host = ASSET_KPTR(func_kernel<F, 2, true>);
+    ASSET_KERNELS(ASSET_X_FILL)
     return r;
   }();
   return &t;
 }
+#undef ASSET_FILL_LGLG
+#undef ASSET_FILL_LGL
+#undef ASSET_FILL_NONE
+#undef ASSET_FILL_FUNC
+#undef ASSET_FILL_BUNDLE
+#undef ASSET_X_FILL
 #undef ASSET_KPTR
 
 struct StaticEntry {   // (static initialisation: the table is filled and the entry registered before main)
@@ -565,61 +601,29 @@ struct StaticEntry {   // (static initialisation: the table is filled and the en
   static ::asset_hip::StaticEntry entry_##ODE##_##CSV##_##BLK(ODE::name(), ::asset_hip::lgl_static_table<ODE, CSV, (BLK != 0), G>());
 
 // ---- name expressions of the kernels of a run-time module (capi.hip: asset_hip_jit_plugin) -----------------------------
-// kind 1: `type` is the ODE functor, kind 2: the function functor, kind 3: the functor list of a bundle.  Slots without a kernel for that kind: empty string.
+// kind 1: `type` is the ODE functor, kind 2: the function functor, kind 3: the comma-separated functor list of a bundle.  Slots
+// without a kernel for that kind: empty string.
 inline std::string rtc_kernel_expr(int slot, int kind, const std::string& type, int csv, bool blocked, int g) {
-  const std::string b = blocked ? "true" : "false";
-  const std::string lgl = type + ", " + std::to_string(csv) + ", " + b;
-  auto tf = [](bool v) { return std::string(v ? "true" : "false"); };
-  if (kind == 3) {   // a bundle: `type` is the comma-separated functor list
-    for (int lv = 0; lv <= 2; lv++)
-      if (slot == K_BUNDLE(lv)) return "asset_hip::func_bundle_kernel<" + std::to_string(lv) + ", " + type + ">";
-    return "";
-  }
-  if (kind == 2) {
-    for (int lv = 0; lv <= 2; lv++)
-      for (int as = 0; as <= (lv >= 1 ? 1 : 0); as++)
-        if (slot == K_FUNC(lv, as != 0)) return "asset_hip::func_kernel<" + type + ", " + std::to_string(lv) + ", " + tf(as != 0) + ">";
-    return "";
-  }
-  for (int lv = 0; lv <= 2; lv++)
-    for (int stg = 1; stg <= 4; stg++)
-      for (int as = 0; as <= 1; as++) {
-        if (slot != K_LGL(lv, stg, as != 0)) continue;
-        const bool used = (stg == 1 && !as) || (stg == 2 && lv >= 1) || (stg == 3 && lv >= 1) || (stg == 4 && lv == 2 && !as);
-        if (!used) return "";
-        return "asset_hip::lgl_defect_kernel<" + lgl + ", " + std::to_string(g) + ", " + std::to_string(lv) + ", " +
-               std::to_string(stg) + ", " + tf(as != 0) + ">";
-      }
-  for (int lv = 1; lv <= 2; lv++)
-    for (int as = 0; as <= 1; as++)
-      if (slot == K_WIDE(lv, as != 0)) return "asset_hip::lgl_wide_dense_kernel<" + lgl + ", " + std::to_string(lv) + ", " + tf(as != 0) + ">";
-  if (slot == K_WIDE_SETUP) return "asset_hip::wide_setup_kernel<" + lgl + ">";
-  if (slot == K_ROWS) return "asset_hip::lgl_rows_kernel<" + lgl + ", 2>";
-  if (slot == K_ROWS1) return "asset_hip::lgl_rows_kernel<" + lgl + ", 1>";
-  if (slot == K_RES(false)) return "asset_hip::lgl_resident_kernel<" + lgl + ", 2, false>";
-  if (slot == K_RES(true)) return "asset_hip::lgl_resident_kernel<" + lgl + ", 2, true>";
-  if (slot == K_RES1(false)) return "asset_hip::lgl_resident_kernel<" + lgl + ", 1, false>";
-  if (slot == K_RES1(true)) return "asset_hip::lgl_resident_kernel<" + lgl + ", 1, true>";
-  for (int lv = 1; lv <= 2; lv++)
-    for (int as = 0; as <= 1; as++)
-      if (slot == K_RESL(lv, as != 0)) return "asset_hip::lgl_resident_kernel<" + lgl + ", " + std::to_string(lv) + ", " + tf(as != 0) + ", true>";
-  if (slot == K_RESLP) return "asset_hip::lgl_resident_kernel<" + lgl + ", 2, false, true, false, true>";
-  if (slot == K_RES_ALT) return "asset_hip::lgl_resident_kernel<" + lgl + ", 2, false, false, false, false, 1>";
-  if (slot == K_RESD(false)) return "asset_hip::lgl_resident_kernel<" + lgl + ", 2, false, true, true>";
-  if (slot == K_RESD(true)) return "asset_hip::lgl_resident_kernel<" + lgl + ", 2, true, true, true>";
-  if (slot == K_RES_SETUP) return "asset_hip::res_lane_setup_kernel<" + lgl + ">";
-  if (slot == K_LANE_SETUP1) return "asset_hip::lane_setup_kernel<" + lgl + ", 1>";
-  if (slot == K_LANE_SETUP2) return "asset_hip::lane_setup_kernel<" + lgl + ", 2>";
-  if (slot == K_UNITS0) return "asset_hip::lgl_ode_units_kernel<" + lgl + ", 0>";
-  if (slot == K_UNITS1) return "asset_hip::lgl_ode_units_kernel<" + lgl + ", 1>";
-  if (slot == K_UNITSJ) return "asset_hip::lgl_ode_units_kernel<" + lgl + ", 3>";
-  if (slot == K_UNITS4) return "asset_hip::lgl_ode_units_kernel<" + lgl + ", 4>";
-  if (slot == K_ADJGRAD) return "asset_hip::lgl_adjgrad_kernel<" + lgl + ", true>";
-  if (slot == K_VALUE) return "asset_hip::lgl_adjgrad_kernel<" + lgl + ", false>";
-  if (slot == K_MESH_YVEC) return "asset_hip::mesh_yvec_kernel<" + lgl + ">";
-  if (slot == K_MESH_ERROR) return "asset_hip::mesh_error_kernel<0>";
-  if (slot == K_INTERP_XDOT) return "asset_hip::interp_xdot_kernel<" + lgl + ">";
-  if (slot == K_INTERP_EVAL) return "asset_hip::interp_eval_kernel<" + lgl + ">";
+  const std::string none, lgl = type + ", " + std::to_string(csv) + ", " + (blocked ? "true" : "false"), lglg = lgl + ", " + std::to_string(g);
+  // (module kind that has the slot, what the family puts before the trailing arguments -- a bundle: after them)
+  auto expr = [&](const char* tmpl, std::string trailing, int slot_kind, const std::string& lead, bool lead_last = false) {
+    if (slot_kind != kind) return std::string();
+    const std::string a = lead_last ? trailing : lead, b = lead_last ? lead : trailing;
+    return "asset_hip::" + std::string(tmpl) + "<" + a + (a.empty() || b.empty() ? "" : ", ") + b + ">";
+  };
+#define ASSET_RTC_LGLG 1, lglg
+#define ASSET_RTC_LGL 1, lgl
+#define ASSET_RTC_NONE 1, none
+#define ASSET_RTC_FUNC 2, type
+#define ASSET_RTC_BUNDLE 3, type, true
+#define ASSET_X_EXPR(NAME, FAMILY, COND, T, ...) case NAME: return expr(#T, #__VA_ARGS__, ASSET_RTC_##FAMILY);
+  switch (slot) { ASSET_KERNELS(ASSET_X_EXPR) }
+#undef ASSET_X_EXPR
+#undef ASSET_RTC_LGLG
+#undef ASSET_RTC_LGL
+#undef ASSET_RTC_NONE
+#undef ASSET_RTC_FUNC
+#undef ASSET_RTC_BUNDLE
   return "";
 }
 

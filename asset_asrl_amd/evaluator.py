@@ -149,6 +149,12 @@ class DefectEvaluator(_KktLayout):
         self._nvalues = -1
         return self
 
+    def launch_plan(self, what: int, assembled: bool = False):
+        """What one evaluation of this handle launches (asset_hip_defect_launch_plan; see _lib.launch_plan)."""
+        p = _lib.LaunchPlan()
+        _lib.check(_lib.lib().asset_hip_defect_launch_plan(self._h, what, int(assembled), C.byref(p)), "asset_hip_defect_launch_plan")
+        return _lib._plan_rows(p)
+
     def close(self):
         h, self._h = getattr(self, "_h", None), None
         if h and _lib is not None and getattr(_lib, "lib", None) is not None:   # module globals vanish at interpreter exit

@@ -156,6 +156,32 @@ int asset_hip_defect_kkt_layout(asset_hip_defect_t h, int* stride, int32_t* rows
  * per block (may be NULL). */
 int asset_hip_kkt_layout(const char* ode, int mode, int blocked, int* nkkt, int* stride, int32_t* rows, int32_t* cols);
 
+/* What one evaluation launches, without a handle or a device: the plan the launcher makes (csrc/registry.h: plan_lgl) for a
+ * compiled transcription (ode, mode, blocked) of an ODE, an evaluation kind `what` (ASSET_HIP_CON ...; no option bits),
+ * assembled != 0 for the on-device assembly kinds (what >= ASSET_HIP_JAC), a mesh of nseg segments and a device of cus compute
+ * units (256 on an MI355X) -- with the default dispatch: the tuning knobs of the measurement scripts are not consulted.  At most
+ * three launches, in order; each a kernel slot (asset_hip_kernel_slot_name gives its name, NULL out of range), grid, block, dynamic
+ * LDS bytes and the kernel's second argument (0: none, 1: `group`, segments per workgroup row of a unit kernel, 2: the workspace
+ * read-only); units_gp: EvalArgs::units_gp of the last launch (> 0: the dense part follows the XCD placement of the unit stage).
+ * ASSET_HIP_ENOODE when the shape is unknown or lacks a kernel the plan names.  asset_hip_defect_launch_plan: the same for a
+ * handle -- its own mesh, device and lane records -- so that run-time compiled shapes can be asked too.
+ * asset_hip_kernel_slot_kinds: which kinds of run-time module name the slot (bit 0: transcription of an ODE, bit 1: plain
+ * function, bit 2: bundle; see asset_hip_jit_compile). */
+typedef struct asset_hip_plan_step {
+  int slot, grid_x, grid_y, block;
+  long long lds_bytes;
+  int extra_arg, group;
+} asset_hip_plan_step;
+typedef struct asset_hip_launch_plan {
+  int nsteps, units_gp;
+  asset_hip_plan_step step[3];
+} asset_hip_launch_plan;
+int asset_hip_launch_plan_query(const char* ode, int mode, int blocked, int what, int assembled, int nseg, int cus,
+                                asset_hip_launch_plan* out);
+int asset_hip_defect_launch_plan(asset_hip_defect_t h, int what, int assembled, asset_hip_launch_plan* out);
+const char* asset_hip_kernel_slot_name(int slot);
+int asset_hip_kernel_slot_kinds(int slot);
+
 /* Host-pointer evaluation: X[n_primal], L[n_equal] (may be NULL for CON/JAC) are copied in, the requested
  * block arrays (any may be NULL) are copied out.  Synchronous. */
 int asset_hip_defect_eval(asset_hip_defect_t h, int what, const double* X, const double* L, double* fx_blocks,

@@ -95,6 +95,7 @@ AD2_ODE(shape_6_0_0, 6, 0, 0)
 AD2_ODE(shape_8_3_1, 8, 3, 1)
 AD2_ODE(shape_10_4_0, 10, 4, 0)
 AD2_ODE(shape_11_4_0, 11, 4, 0)
+AD2_ODE(shape_2_13_0, 2, 13, 0)
 
 }  // namespace
 
@@ -156,6 +157,7 @@ GEN_DECL(shape_6_0_0)
 GEN_DECL(shape_8_3_1)
 GEN_DECL(shape_10_4_0)
 GEN_DECL(shape_11_4_0)
+GEN_DECL(shape_2_13_0)
 
 extern "C" {
 
@@ -248,6 +250,7 @@ int oracle_get_ode4(const oracle_ode* ode, oracle_ode4* out) {
   TRY4(shape_8_3_1)
   TRY4(shape_10_4_0)
   TRY4(shape_11_4_0)
+  TRY4(shape_2_13_0)
   return -1;
 }
 
@@ -296,6 +299,7 @@ int oracle_get_ode(const char* name, int provider, oracle_ode* out) {
   TRY(shape_8_3_1, 8, 3, 1, nullptr)
   TRY(shape_10_4_0, 10, 4, 0, nullptr)
   TRY(shape_11_4_0, 11, 4, 0, nullptr)
+  TRY(shape_2_13_0, 2, 13, 0, nullptr)
   return -1;
 }
 }

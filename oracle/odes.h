@@ -210,6 +210,7 @@ ORACLE_SHAPE_ODE(6, 0, 0)
 ORACLE_SHAPE_ODE(8, 3, 1)
 ORACLE_SHAPE_ODE(10, 4, 0)
 ORACLE_SHAPE_ODE(11, 4, 0)
+ORACLE_SHAPE_ODE(2, 13, 0)   // N + 1 = 17 with a sparse right-hand side: the fused forms of csrc/defect_kernels.h (STAGE 3 / 4)
 
 // ------------------------------------------------------------------ a nonlinear path constraint, 2 outputs of 6 inputs
 // Not an ODE: the independent check for plain functions batched over applications (mode FUNCTION);

@@ -120,7 +120,7 @@ def make_driven(n: int = 14):
     return Driven()
 
 
-SHAPES = [(1, 0, 0), (1, 1, 0), (2, 1, 0), (3, 0, 1), (4, 4, 0), (5, 3, 2), (6, 0, 0), (8, 3, 1), (10, 4, 0), (11, 4, 0)]
+SHAPES = [(1, 0, 0), (1, 1, 0), (2, 1, 0), (3, 0, 1), (4, 4, 0), (5, 3, 2), (6, 0, 0), (8, 3, 1), (10, 4, 0), (11, 4, 0), (2, 13, 0)]
 
 
 def make_shape(n: int, m: int, p: int):

@@ -133,30 +133,35 @@ def test_ragged_segment_counts(oracle, nseg):
 
 
 @pytest.mark.parametrize("ode,mode,blocked,nseg", [
-    # Reentry-LGL7 on 256 CUs x 8 workgroups: fused up to 7 segments per workgroup (14 336), two launches beyond; the
-    # two-wave form takes shares of exactly 4 (GF2 = 8)
+    # Sizes that bracketed the forms of round 2's launcher (one-wave fused up to 14 336, two-wave fused at shares of 4, two launches
+    # beyond).  Since the resident kernel took these shapes (launch forms) they are ordinary sizes inside its
+    # intervals -- Reentry-LGL7 on 256 CUs: K_RES2 (two-wave workgroups) up to 2 559, K_RES_ALT up to 10 240, K_RESLP beyond
     ("reentry", "LGL7", False, 2047), ("reentry", "LGL7", False, 2049), ("reentry", "LGL7", False, 6145),
     ("reentry", "LGL7", False, 8192), ("reentry", "LGL7", False, 8193), ("reentry", "LGL7", False, 14336),
     ("reentry", "LGL7", False, 14337),
-    # TwoBody-LGL5-BlockConstant: two-wave shares of 4..10 (GF2 = 20), one-wave up to GF = 15, then two launches
+    # TwoBody-LGL5-BlockConstant: K_RES2 up to 10 240, K_RESL2 (single waves) beyond
     ("twobody_lt", "LGL5", True, 6143), ("twobody_lt", "LGL5", True, 8193), ("twobody_lt", "LGL5", True, 20481),
     ("twobody_lt", "LGL5", True, 30719), ("twobody_lt", "LGL5", True, 30721),
-    # Betts (ODE stage in units): fewer segments than one group, a ragged last group
+    # Betts (ODE stage in units, K_UNITS4 + K_RESD): fewer segments than one group, a ragged last group
     ("betts_lowthrust", "LGL5", False, 3), ("betts_lowthrust", "LGL5", False, 1031),
     # ... whose dense part takes its slots one segment ahead (global -> LDS): one segment per wave (nothing ahead), two, groups of
-    # 3 + 2 (slot 0 of the second group asked for by the last segment of the first), three groups
+    # 3 + 2 (slot 0 of the second group asked for by the last segment of the first), three groups; up to 1 031 the dense part follows
+    # the XCD placement of the unit stage (units_gp > 0), at 4 500 and 9 001 it does not
     ("betts_lowthrust", "LGL7", False, 1000), ("betts_lowthrust", "LGL7", False, 1031), ("betts_lowthrust", "LGL7", False, 4500),
     ("betts_lowthrust", "LGL7", False, 9001),
-    # (round 6) shapes with both forms of the dense part (registry.h: alt, lpair): tiles below two and a half segments per workgroup, rows from there to the
-    # end of the one-group kernel, the looped pair kernel (rows) on every looped mesh
+    # shapes with both forms of the dense part (registry.h: plan_lgl, alt / lpair): tiles below two and a half segments per workgroup
+    # (K_RES2 to 2 559), rows from there to the end of the one-group kernel (K_RES_ALT to 10 240; Reentry-LGL3 x 6 200), the looped pair
+    # kernel (rows) on every looped mesh (K_RESLP; Reentry-LGL5 x 43 100)
     ("reentry", "LGL7", False, 2559), ("reentry", "LGL7", False, 2560), ("reentry", "LGL7", False, 6143), ("reentry", "LGL7", False, 6144),
     ("reentry", "LGL7", False, 10240), ("reentry", "LGL7", False, 10241), ("reentry", "LGL7", False, 15000),
     ("reentry", "LGL7", False, 30720), ("reentry", "LGL7", False, 30721), ("reentry", "LGL3", False, 6200), ("reentry", "LGL5", False, 43100),
-    # light right-hand sides keep single-wave workgroups on looped meshes (ResDims::LOOP_PAIR)
+    # light right-hand sides keep single-wave workgroups on looped meshes (ResDims::LOOP_PAIR): K_RESL2
     ("twobody_lt", "LGL5", True, 60003), ("brachistochrone", "LGL7", False, 40001)])
 def test_launch_form_boundaries(oracle, ode, mode, blocked, nseg):
-    """Mesh sizes on either side of every switch of the launcher (csrc/registry.h: launch_lgl_table): one-wave fused,
-    two-wave fused, ODE stage + dense stage, units -- every block against the oracle."""
+    """Mesh sizes on either side of the switches of the launcher (csrc/registry.h: plan_lgl) that library shapes meet at level 2:
+    the resident kernel as one group of tiles, one group of rows, looped pair, looped single waves; the unit stage with and
+    without XCD placement of the dense part -- every block against the oracle.  Which form a size takes is asserted without a
+    device by tests/test_launch_plan_cpu.py; the fused forms of csrc/defect_kernels.h (STAGE 3 / 4) are planned for no library shape."""
     w = Workload(ode, mode, nseg, blocked)
     ev = DefectEvaluator(ode, mode, blocked, w.vindex, w.cindex, w.n_primal, w.n_equal)
     ref = w.oracle_nlp(oracle, threads=8).eval_blocks(oracle.JAC_ADJGRAD_HESS, w.X, w.L)
