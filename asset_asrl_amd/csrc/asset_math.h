@@ -40,7 +40,8 @@ ASSET_MATH_FN void asset_sincos(double x, double* sp, double* cp) {
   const double c = fma(z * z, pc, fma(z, -0.5, 1.0));
   const int q = static_cast<int>(fn - 4.0 * floor(fn * 0.25));   // fn mod 4 without leaving the double range
   const double ss = (q & 1) ? c : s, cc = (q & 1) ? s : c;
-  *sp = (q & 2) ? -ss : ss;
+  // sin(-0.0) is -0.0: the correction term r z ps has the sign opposite to r, so for r = -0.0 the sum above is +0.0 + -0.0 = +0.0
+  *sp = (x == 0.0) ? x : ((q & 2) ? -ss : ss);
   *cp = ((q + 1) & 2) ? -cc : cc;
 }
 ASSET_MATH_FN double asset_sin(double x) { double s, c; asset_sincos(x, &s, &c); return s; }

@@ -329,6 +329,10 @@ class Condition:
     def __or__(self, other):
         return self._join(other, "or")
 
+    def __bool__(self):
+        # (``0.0 < x < 1.0`` and ``(a > b) and (c < d)`` go through bool(): Python would keep one test and silently drop the other)
+        raise TypeError("use & / | to join conditions")
+
     def compute(self, x) -> bool:
         return bool(evaluate([self.node], np.asarray(x, dtype=float).ravel())[0])
 

@@ -366,10 +366,16 @@ class Graph:
         raise ValueError(op)
 
     # ---- reverse sweep: gradient of one scalar wrt a set of leaves ------------------
-    def grad(self, s: Node, wrts: Sequence[Node]) -> List[Node]:
-        """Reverse-mode gradient of scalar node s with respect to the given leaves."""
+    def grad(self, s: Node, wrts: Sequence[Node], seed: Node = None) -> List[Node]:
+        """Reverse-mode gradient of scalar node s with respect to the given leaves, times ``seed`` (the adjoint of s; default 1).
+
+        A select is differentiated BRANCH BY BRANCH: each branch gets a reverse sweep of its own, seeded with the adjoint of the
+        select, and the leaves receive ``select(c, g_true, g_false)`` -- the select stays outermost, as in the forward rule of
+        ``d``, and as the reference's IfElseFunction evaluates the derivatives of the taken branch only (Conditional.h:215-250).
+        Pushing ``select(c, bar, 0)`` into the branches instead multiplies a zero adjoint with the local derivatives of the branch
+        that was NOT taken, and where a test guards a sqrt, a log or a quotient those are Inf / NaN: 0 * NaN = NaN in g and H."""
         order = topo_order([s])
-        adj: Dict[int, Node] = {s.id: self.one}
+        adj: Dict[int, Node] = {s.id: self.one if seed is None else seed}
         for n in reversed(order):
             bar = adj.get(n.id)
             if bar is None or bar is self.zero or not n.args:
@@ -381,8 +387,9 @@ class Graph:
                 continue
             if op == "select":
                 c, a, b = n.args
-                self._acc(adj, a, self.select(c, bar, self.zero))
-                self._acc(adj, b, self.select(c, self.zero, bar))
+                ga, gb = self.grad(a, wrts, bar), self.grad(b, wrts, bar)
+                for w, x, y in zip(wrts, ga, gb):
+                    self._acc(adj, w, self.select(c, x, y))
                 continue
             if op in _UNARY or op in ("powi", "powr"):
                 a = n.args[0]
@@ -414,6 +421,8 @@ class Graph:
 
     def _acc(self, adj, n: Node, v: Node):
         if n.is_const():
+            return
+        if v is self.zero:
             return
         cur = adj.get(n.id)
         adj[n.id] = v if cur is None else self.add(cur, v)
@@ -548,53 +557,76 @@ def frontier(roots: Sequence[Node]):
 
 
 def evaluate(roots: Sequence[Node], y: Sequence[float], lam: Sequence[float] = (), aconst: Sequence[float] = ()) -> List[float]:
-    """Host-side numeric walk of the DAG (set-up time checks only, never the hot path)."""
+    """Host-side numeric walk of the DAG (set-up time checks only, never the hot path).  Demand driven: of a select only the test and
+    the branch it picks are evaluated, as in the reference's IfElseFunction -- the other branch may lie outside its domain there
+    (a guarded sqrt, log or quotient) and is never touched."""
     val: Dict[int, float] = {}
-    for n in topo_order(roots):
+    stack: List[Node] = list(reversed(list(roots)))
+    while stack:
+        n = stack[-1]
+        if n.id in val:
+            stack.pop()
+            continue
         op = n.op
-        if op == "const":
-            v = n.value
-        elif op == "var":
-            v = float(y[n.value])
-        elif op == "lam":
-            v = float(lam[n.value])
-        elif op == "aconst":
-            v = float(aconst[n.value])
-        elif op == "add":
-            v = val[n.args[0].id] + val[n.args[1].id]
-        elif op == "sub":
-            v = val[n.args[0].id] - val[n.args[1].id]
-        elif op == "mul":
-            v = val[n.args[0].id] * val[n.args[1].id]
-        elif op == "div":
-            v = val[n.args[0].id] / val[n.args[1].id]
-        elif op == "neg":
-            v = -val[n.args[0].id]
-        elif op == "powi":
-            v = val[n.args[0].id] ** n.value
-        elif op == "powr":
-            v = val[n.args[0].id] ** n.value
-        elif op == "atan2":
-            v = math.atan2(val[n.args[0].id], val[n.args[1].id])
-        elif op == "cut":
-            v = val[n.args[0].id]
-        elif op in _COMPARE:
-            v = float(_EVAL_COND[op](val[n.args[0].id], val[n.args[1].id]))
-        elif op == "and":
-            v = float(val[n.args[0].id] != 0.0 and val[n.args[1].id] != 0.0)
-        elif op == "or":
-            v = float(val[n.args[0].id] != 0.0 or val[n.args[1].id] != 0.0)
-        elif op == "select":
-            v = val[n.args[1].id] if val[n.args[0].id] != 0.0 else val[n.args[2].id]
-        elif op == "tabloc":
-            v = float(TABLES[n.value].locate(val[n.args[0].id]))
-        elif op == "tabget":
-            dg, arr, row, off = n.value
-            v = float(_tab_entry(TABLES[dg], arr, row, int(val[n.args[0].id]) + off))
-        else:
-            v = _EVAL_UNARY[op](val[n.args[0].id])
-        val[n.id] = v
+        if op == "select":
+            c = n.args[0]
+            if c.id not in val:
+                stack.append(c)
+                continue
+            taken = n.args[1] if val[c.id] != 0.0 else n.args[2]
+            if taken.id not in val:
+                stack.append(taken)
+                continue
+            val[n.id] = val[taken.id]
+            stack.pop()
+            continue
+        missing = [a for a in n.args if a.id not in val]
+        if missing:
+            stack.extend(reversed(missing))
+            continue
+        stack.pop()
+        val[n.id] = _eval_node(n, [val[a.id] for a in n.args], y, lam, aconst)
     return [val[r.id] for r in roots]
+
+
+def _eval_node(n: Node, a: List[float], y, lam, aconst) -> float:
+    op = n.op
+    if op == "const":
+        return n.value
+    if op == "var":
+        return float(y[n.value])
+    if op == "lam":
+        return float(lam[n.value])
+    if op == "aconst":
+        return float(aconst[n.value])
+    if op == "add":
+        return a[0] + a[1]
+    if op == "sub":
+        return a[0] - a[1]
+    if op == "mul":
+        return a[0] * a[1]
+    if op == "div":
+        return a[0] / a[1]
+    if op == "neg":
+        return -a[0]
+    if op in ("powi", "powr"):
+        return a[0] ** n.value
+    if op == "atan2":
+        return math.atan2(a[0], a[1])
+    if op == "cut":
+        return a[0]
+    if op in _COMPARE:
+        return float(_EVAL_COND[op](a[0], a[1]))
+    if op == "and":
+        return float(a[0] != 0.0 and a[1] != 0.0)
+    if op == "or":
+        return float(a[0] != 0.0 or a[1] != 0.0)
+    if op == "tabloc":
+        return float(TABLES[n.value].locate(a[0]))
+    if op == "tabget":
+        dg, arr, row, off = n.value
+        return float(_tab_entry(TABLES[dg], arr, row, int(a[0]) + off))
+    return _EVAL_UNARY[op](a[0])
 
 
 GRAPH = Graph()

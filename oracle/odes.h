@@ -19,6 +19,7 @@ namespace oracle_odes {
 
 using std::cos;
 using std::exp;
+using std::log;
 using std::sin;
 using std::sqrt;
 using std::tan;
@@ -60,6 +61,20 @@ void switched(const S* y, S* f, const void*) {
   const double dir = (valof(x1) > 0.0) - (valof(x1) < 0.0);          // sign(x1): piecewise constant, no derivative
   f[0] = x1 + (valof(t) < 5.0 ? S(0.1 * sin(x0)) : S(0.0 * x0));
   f[1] = -1.0 * spring - 0.3 * absv(x1) * x1 - 0.05 * dir + u * cos(t);
+}
+
+// ------------------------------------------------------------------ guarded branches (2,1,0): a test that protects a sqrt, a log, a quotient
+// Not a BASELINE config: the independent check that an ifelse whose other branch lies OUTSIDE its domain stays finite in every
+// derivative (the reference's IfElseFunction evaluates the branch the test picks and nothing of the other one,
+// CommonFunctions/Conditional.h:151-260).  Plain C++ branches: AD2 never sees the branch that is not taken.
+// tests/helpers.py: make_guarded defines the same right-hand side in the product's expression DSL.
+template <class S>
+void guarded(const S* y, S* f, const void*) {
+  const S &x0 = y[0], &x1 = y[1], &t = y[2], &u = y[3];
+  f[0] = (valof(x0) > 0.0 ? S(sqrt(x0) * x1) : S(x1 * u)) + 0.1 * cos(t);
+  const S lg = valof(x1) > 0.5 ? S(log(x1 - 0.5) * u) : S(0.0 * x0);
+  const S qt = (valof(u) > 0.0 || valof(u) < 0.0) ? S(x0 / u) : S(x0 * 1.0);
+  f[1] = lg - 0.3 * x0 + qt;
 }
 
 // ------------------------------------------------------------------ a sounding rocket on tabulated data (2,1,0): InterpTable1D

@@ -280,6 +280,46 @@ def make_switched():
     return Switched()
 
 
+def make_guarded():
+    """A user ODE whose conditionals GUARD a sqrt, a log and a quotient (2, 1, 0): on the other side of each test, and exactly on it,
+    the branch that is not taken lies outside its domain (NaN, -Inf, a division by zero) and nothing of it may reach f, J, g or H.
+    The oracle holds the same right-hand side as ``guarded`` (oracle/odes.h) with plain C++ branches, differentiated by AD2."""
+    from asset_asrl_amd import vf
+    from asset_asrl_amd.ode import ODEArguments, ODEBase
+
+    class Guarded(ODEBase):
+        def __init__(self):
+            a = ODEArguments(2, 1, 0)
+            x0, x1 = a.XVec().tolist()
+            t, u = a.TVar(), a.UVar(0)
+            f0 = vf.ifelse(x0 > 0.0, vf.sqrt(x0) * x1, x1 * u) + 0.1 * vf.cos(t)
+            f1 = vf.ifelse(x1 > 0.5, vf.log(x1 - 0.5) * u, 0.0) - 0.3 * x0 + vf.ifelse((u > 0.0) | (u < 0.0), x0 / u, x0)
+            super().__init__(vf.stack([f0, f1]), 2, 1, 0, name="guarded")
+
+    return Guarded()
+
+
+def guarded_workload(mode: str, blocked: bool, nseg: int = 83):
+    """A phase of ``guarded`` with states on both sides of every guard and EXACTLY on it: x0 = 0.0, x1 = 0.5, u = 0.0 at some of the
+    states (the controls of a BlockConstant phase: one value per segment behind the states), |u| >= 0.2 elsewhere."""
+    w = Workload("guarded", mode, nseg, blocked, sizes=(2, 1, 0), var_offset=1, con_offset=2, extra_vars=2)
+    ix = w.indexer
+    S = ix.numStates
+    xtu = ix.XtVars() if w.blocked else ix.XtUVars()
+    st = w.X[1:1 + S * xtu].reshape(S, xtu)                                # (a view: the solver vector itself is changed)
+    st[:, 1] = 0.5 + 1.5 * st[:, 1]                                        # x1 in (-1, 2): both sides of 0.5
+    st[::5, 0] = 0.0
+    st[2::7, 1] = 0.5
+    if w.blocked:
+        assert ix.numPhaseVars == S * xtu + nseg
+        ctrl = w.X[1 + S * xtu:1 + S * xtu + nseg]
+    else:
+        ctrl = st[:, 3]
+    ctrl[:] = np.where(ctrl < 0.0, -1.0, 1.0) * np.maximum(np.abs(ctrl), 0.2)
+    ctrl[1::6] = 0.0
+    return w
+
+
 def tabulated_tables():
     """The three tables of the oracle's `tabulated` ODE (oracle/interp_table.h: tabulated_table), built here from the same
     arithmetic as ``vf.InterpTable1D`` objects through three of the reference's constructors (InterpTable1D.h:409-424)."""

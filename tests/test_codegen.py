@@ -174,3 +174,46 @@ def test_conditionals_abs_and_sign_match_oracle_ad2(oracle):
     assert "? " in emit_c(d, "ode_switched") and "&&" in emit_hip_functor(d, "OdeSwitched")
     with pytest.raises(ValueError):
         vf.ifelse(vf.Arguments(2)[0], 1.0, 2.0)                       # the test must be a comparison
+
+
+def test_guarded_branches_match_oracle_ad2(oracle):
+    """Conditionals that GUARD a sqrt, a log and a quotient: on the other side of the test, and exactly on it, the branch that is not
+    taken is NaN / -Inf / a division by zero, and nothing of it may reach J, g or H -- the select stays outermost in the reverse sweep
+    too (vf/ir.py: Graph.grad), as the reference's IfElseFunction evaluates the taken branch only.  Against the oracle's AD2 derivatives
+    of the same right-hand side with plain C++ branches (oracle/odes.h: guarded), through ``ir.evaluate`` and through the compiled C."""
+    from helpers import make_guarded
+    ode = make_guarded()
+    d = ode.derivatives()
+    o = oracle.get_ode("guarded", 0)
+    N, n = d.nin, d.xv
+    with tempfile.TemporaryDirectory() as tmp:
+        src, so = os.path.join(tmp, "g.c"), os.path.join(tmp, "g.so")
+        with open(src, "w") as fh:
+            fh.write(emit_c(d, "ode_guarded"))
+        subprocess.check_call(["gcc", "-O1", "-shared", "-fPIC", src, "-o", so, "-lm"])
+        L = C.CDLL(so)
+        rng = np.random.default_rng(5)
+        fn = C.CFUNCTYPE(None, *([C.c_void_p] * 7))(o.fjgh)
+        sides = set()
+        for k in range(300):
+            y = rng.uniform(-1, 1, N)
+            y[1] = rng.uniform(-0.5, 1.5)
+            if k % 5 == 0:
+                y[0] = 0.0
+            if k % 7 == 0:
+                y[1] = 0.5
+            if k % 6 == 0:
+                y[3] = 0.0
+            lam = rng.uniform(-1, 1, n)
+            sides.add((float(np.sign(y[0])), float(np.sign(y[1] - 0.5)), float(np.sign(y[3]))))
+            f, J, g, H = np.zeros(n), np.zeros((n, N)), np.zeros(N), np.zeros((N, N))
+            fn(y.ctypes.data, lam.ctypes.data, f.ctypes.data, J.ctypes.data, g.ctypes.data, H.ctypes.data, o.ctx)
+            assert all(np.all(np.isfinite(a)) for a in (f, J, g, H))
+            Hs = evaluate([d.H[max(i, j)][min(i, j)] for i in range(N) for j in range(N)], y, lam)
+            got = (evaluate(d.f, y), evaluate([e for r in d.J for e in r], y), evaluate(d.g, y, lam), Hs)
+            f2, J2, g2, H2 = np.zeros(n), np.zeros((n, N)), np.zeros(N), np.zeros((N, N))
+            L.ode_guarded_fjgh(*[C.c_void_p(a.ctypes.data) for a in (y, lam, f2, J2, g2, H2)])
+            for a, b, c, tol in zip(got, (f2, J2, g2, H2), (f, J, g, H), (1e-14, 1e-13, 1e-13, 1e-13)):
+                assert np.all(np.isfinite(a)) and np.all(np.isfinite(b))
+                assert rel_err(np.asarray(a).reshape(c.shape), c) < tol and rel_err(b, c) < tol
+        assert len(sides) == 27                        # below, on and above every guard, in every combination
