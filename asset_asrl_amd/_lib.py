@@ -64,6 +64,8 @@ SYMBOLS = {
                                                                                          C.POINTER(C.c_float)]),
     "asset_hip_defect_set_appl_consts": (C.c_int, [C.c_void_p, _dp, C.c_int]),
     "asset_hip_defect_set_kkt_map": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_longlong, C.c_int]),
+    "asset_hip_kkt_map_query": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _ip, C.c_longlong, C.c_int, C.POINTER(C.c_longlong), _ip,
+                                         C.POINTER(C.c_int), _ip, _ip, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]),
     "asset_hip_defect_eval_assembled": (C.c_int, [C.c_void_p, C.c_int, _dp, _dp, _dp, _dp, _dp]),
     "asset_hip_defect_eval_assembled_zeroed": (C.c_int, [C.c_void_p, C.c_int, _dp, _dp, _dp, _dp, _dp]),
     "asset_hip_defect_eval_assembled_device": (C.c_int, [C.c_void_p, C.c_int] + [C.c_void_p] * 6),
@@ -163,6 +165,21 @@ def launch_plan(name: str, mode: int, blocked: bool, what: int, assembled: bool,
     check(lib().asset_hip_launch_plan_query(name.encode(), mode, int(blocked), what, int(assembled), nseg, cus, C.byref(p)),
           "asset_hip_launch_plan_query")
     return _plan_rows(p)
+
+
+def kkt_map(ir: int, orr: int, plain_function: bool, slot_locations, nvalues: int, accumulate: bool = False):
+    """(map words, multi_ptr, multi_loc, lo, hi): what asset_hip_defect_set_kkt_map uploads for ``slot_locations[nseg, NKKT]`` of a
+    function with ``ir`` input and ``orr`` output rows: asset_hip_kkt_map_query -- no handle, no device."""
+    m = np.ascontiguousarray(slot_locations, dtype=np.int32)
+    nseg = m.size // (ir * (ir + 1) // 2 + orr * ir)
+    n, nm, lo, hi = C.c_longlong(), C.c_int(), C.c_longlong(), C.c_longlong()
+    head = (ir, orr, int(plain_function), nseg, m.ctypes.data_as(_ip), int(nvalues), int(accumulate))
+    check(lib().asset_hip_kkt_map_query(*head, C.byref(n), None, C.byref(nm), None, None, C.byref(lo), C.byref(hi)),
+          "asset_hip_kkt_map_query")
+    words, ptr, loc = np.empty(n.value, np.int32), np.empty(nm.value + 1, np.int32), np.empty(nm.value, np.int32)
+    check(lib().asset_hip_kkt_map_query(*head, None, words.ctypes.data_as(_ip), None, ptr.ctypes.data_as(_ip), loc.ctypes.data_as(_ip),
+                                        None, None), "asset_hip_kkt_map_query")
+    return words, ptr, loc, lo.value, hi.value
 
 
 def has_kernel(name: str, mode: int, blocked: bool) -> bool:

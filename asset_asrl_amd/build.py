@@ -144,6 +144,8 @@ def _compile(src):
     os.makedirs(OBJ, exist_ok=True)
     obj = os.path.join(OBJ, os.path.basename(src).rsplit(".", 1)[0] + ".o")
     deps = [src] + [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")]
+    if os.path.basename(src).startswith("capi"):        # host-only headers: no device unit (and no run-time module) depends on them
+        deps += [os.path.join(CSRC, "capi", f) for f in os.listdir(os.path.join(CSRC, "capi")) if f.endswith(".h")]
     for f in os.listdir(GEN):
         if f.startswith("ode_") and f.endswith(".h") and f'#include "{f}"' in open(src).read():
             deps.append(os.path.join(GEN, f))

@@ -21,6 +21,8 @@
 #include <unistd.h>
 
 #include "registry.h"
+#include "capi/kkt_map.h"
+#include "capi/owners.h"
 
 namespace asset_hip {
 // values[loc[l]] = sum of stage[ptr[l] .. ptr[l+1]) in a FIXED order: thread t of the block adds cells t, t+256, ... in
@@ -79,11 +81,26 @@ int hipfail(hipError_t e, const char* where) {
   g_err = std::string(where) + ": " + hipGetErrorString(e);
   return int(e) > 0 ? int(e) : ASSET_HIP_ENODEV;
 }
-#define HIP_TRY(expr)                                     \
+#define HIP_TRY_AS(expr, where)                           \
   do {                                                    \
     hipError_t _e = (expr);                               \
-    if (_e != hipSuccess) return hipfail(_e, #expr);      \
+    if (_e != hipSuccess) return hipfail(_e, where);      \
   } while (0)
+#define HIP_TRY(expr) HIP_TRY_AS(expr, #expr)
+
+using asset_hip::DeviceBuffer;
+using asset_hip::PinnedBuffer;
+using asset_hip::stream_or;
+using asset_hip::use_device;
+using asset_hip::wants_kkt;
+using asset_hip::wants_multipliers;
+
+// v on the device, in a buffer of v.size() + pad elements
+template <class T>
+hipError_t upload(DeviceBuffer<T>& dst, const std::vector<T>& v, size_t pad = 0) {
+  const hipError_t e = dst.allocate(v.size() + pad);
+  return e != hipSuccess ? e : hipMemcpy(dst.get(), v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice);
+}
 
 const asset_hip::KernelEntry* find_entry(const char* ode, int mode, int blocked) {
   for (auto* e = asset_hip::registry_head(); e; e = e->next)
@@ -104,45 +121,47 @@ int level_of(int what) {
 
 }  // namespace
 
+// Members are grouped by what invalidates them: a group is dropped by assigning an empty one, and a new one is built in a local and
+// committed by one move.  The stream and the events come first, so they go last: buffers, then events, then the stream.
 struct asset_hip_defect {
   const asset_hip::KernelEntry* ke = nullptr;
   int nseg = 0, n_primal = 0, n_equal = 0, device = 0;
   int cus = 256;
-  // what the buffers below were sized for (asset_hip_defect_rebind keeps them while the new mesh fits)
-  int cap_seg = 0, cap_primal = 0, cap_equal = 0;
-  int* d_vindex = nullptr;
-  int* d_cindex = nullptr;
-  // staging for the host-pointer entry point (allocated lazily)
-  double *d_X = nullptr, *d_L = nullptr, *d_fx = nullptr, *d_agx = nullptr, *d_kkt = nullptr;
-  double* d_work = nullptr;  // per-workgroup ODE result slots
-  void* d_lane[3] = {nullptr, nullptr, nullptr};   // per-lane constants of the dense stage by derivative level
-  double* d_aconst = nullptr;      // constants of every application of a plain function (asset_hip_defect_set_appl_consts)
-  // on-device KKT assembly (asset_hip_defect_set_kkt_map)
-  int32_t* d_map = nullptr;        // value location of every accumulator entry, fragment order (defect_kernels.h, ASM)
-  size_t map_len = 0;
-  double* d_values = nullptr;      // [value_hi - value_lo) staging for the host-pointer entry point
-  double* h_values = nullptr;      // pinned mirror of d_values
-  long long value_lo = 0, value_hi = 0, nvalues = 0;
-  // locations with three or more contributing slots: staged cells + fixed-order reduction (defect_dims.h, asm_reduce_kernel)
-  double* d_stage = nullptr;
-  int *d_multi_ptr = nullptr, *d_multi_loc = nullptr;
-  int nmulti = 0;
-  size_t nstage = 0;
-  // device RHS fill (asset_hip_defect_eval_kkt_device): CSR by target row over the FX / AGX block entries
-  int *d_fx_rows = nullptr, *d_fx_ptr = nullptr, *d_fx_src = nullptr, *d_gx_rows = nullptr, *d_gx_ptr = nullptr, *d_gx_src = nullptr;
-  int n_fx_rows = 0, fx_long_from = 0, n_gx_rows = 0, gx_long_from = 0;
-  bool rhs_tables_ready = false;
-  int affine = 0, aff_v0 = 0, aff_vs = 0, aff_c0 = 0, aff_cs = 0;   // index rows that are runs (EvalArgs::affine)
   int bundles = 0;                   // bundles that hold this handle (asset_hip_bundle_create)
   bool destroy_pending = false;      // asset_hip_defect_destroy was called while a bundle held it: freed with the last bundle
-  double *d_fxb = nullptr, *d_agxb = nullptr;    // block buffers of that entry point
-  std::vector<int32_t> h_vindex, h_cindex;       // kept for the RHS tables (built on first use)
-  hipStream_t stream = nullptr;
+  asset_hip::Stream stream;
+  asset_hip::Event ev0, ev1;
   // the caller's stream of the last *_device entry point (asset_hip_defect_rebind drains it before it touches the tables those
   // launches read: a torch side stream or hipStreamLegacy is not ordered with the handle's own stream)
   hipStream_t last_stream = nullptr;
   bool last_stream_used = false;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  // what the buffers below were sized for (asset_hip_defect_rebind keeps them while the new mesh fits)
+  int cap_seg = 0, cap_primal = 0, cap_equal = 0;
+  struct MeshTables {
+    DeviceBuffer<int> vindex, cindex;
+    DeviceBuffer<double> work;                        // per-workgroup ODE result slots
+    int affine = 0, aff_v0 = 0, aff_vs = 0, aff_c0 = 0, aff_cs = 0;   // index rows that are runs (EvalArgs::affine)
+    std::vector<int32_t> h_vindex, h_cindex;          // kept for the RHS tables (built on first use)
+  } mesh;
+  struct HostStaging {   // of the host-pointer entry points (allocated lazily, for the capacities above)
+    DeviceBuffer<double> X, L, fx, agx, kkt;
+  } staging;
+  struct DeviceKktMap {  // on-device KKT assembly (asset_hip_defect_set_kkt_map); no map words: no map
+    DeviceBuffer<int32_t> map;                        // value location of every accumulator entry, fragment order (defect_kernels.h, ASM)
+    // locations with three or more contributing slots: staged cells + fixed-order reduction (defect_dims.h, asm_reduce_kernel)
+    DeviceBuffer<double> stage;
+    DeviceBuffer<int32_t> multi_ptr, multi_loc;
+    long long value_lo = 0, value_hi = 0, nvalues = 0;
+    DeviceBuffer<double> d_values;                    // [value_hi - value_lo) staging for the host-pointer entry point
+    PinnedBuffer<double> h_values;                    // pinned mirror of d_values
+  } kmap;
+  struct RhsTables {     // device RHS fill (asset_hip_defect_eval_kkt_device): CSR by target row over the FX / AGX block entries
+    DeviceBuffer<int> fx_rows, fx_ptr, fx_src, gx_rows, gx_ptr, gx_src;
+    int n_fx_rows = 0, fx_long_from = 0, n_gx_rows = 0, gx_long_from = 0;
+    DeviceBuffer<double> fxb, agxb;                   // block buffers of that entry point; agxb is the last to be built
+  } rhs;
+  DeviceBuffer<double> aconst;     // constants of every application of a plain function (asset_hip_defect_set_appl_consts)
+  DeviceBuffer<char> lane[3];      // per-lane constants of the dense stage by derivative level
 };
 
 extern "C" {
@@ -401,57 +420,63 @@ int asset_hip_lgl_table(int cs, const char* which, double* out, int cap) {
   return rows * cols;
 }
 
-// Index tables of a handle: bounds check (the kernels trust them), upload, run detection; buffers that depend on the number of
-// applications are kept while they fit and re-allocated otherwise; everything derived from the OLD tables is dropped.
-static int bind_tables(asset_hip_defect_t h, int nseg, const int32_t* vindex, const int32_t* cindex, int n_primal, int n_equal) {
-  const asset_hip::KernelEntry* ke = h->ke;
+// The kernels trust the index tables: every entry names a row of the solver vector / of the equality constraints
+static int check_index_tables(const asset_hip::KernelEntry* ke, int nseg, const int32_t* vindex, const int32_t* cindex, int n_primal,
+                              int n_equal) {
   const size_t nv = size_t(ke->ir) * nseg, nc = size_t(ke->orr) * nseg;
   for (size_t i = 0; i < nv; i++)
     if (vindex[i] < 0 || vindex[i] >= n_primal) return fail(ASSET_HIP_ERANGE, "vindex entry out of range");
   for (size_t i = 0; i < nc; i++)
     if (cindex[i] < 0 || cindex[i] >= n_equal) return fail(ASSET_HIP_ERANGE, "cindex entry out of range");
-  auto drop = [](auto*& p) { if (p) { (void)hipFree(p); p = nullptr; } };
-  if (h->stream) HIP_TRY(hipStreamSynchronize(h->stream));       // (nothing of the old mesh is in flight on the handle's own stream ...
+  return 0;
+}
+
+// Index tables of a handle (checked by the caller: check_index_tables): upload, run detection; buffers that depend on the number of
+// applications are kept while they fit and re-allocated otherwise; everything derived from the OLD tables is dropped.
+static int bind_tables(asset_hip_defect_t h, int nseg, const int32_t* vindex, const int32_t* cindex, int n_primal, int n_equal) {
+  const asset_hip::KernelEntry* ke = h->ke;
+  const size_t nv = size_t(ke->ir) * nseg, nc = size_t(ke->orr) * nseg;
+  if (h->stream.get()) HIP_TRY(hipStreamSynchronize(h->stream.get()));   // (nothing of the old mesh is in flight on the handle's own stream ...
   if (h->last_stream_used) {                                     //  ... nor on the caller's stream of the last *_device call;
     if (hipStreamSynchronize(h->last_stream) != hipSuccess) (void)hipGetLastError();   //  a stream the caller has destroyed since is drained)
     h->last_stream_used = false;
   }
   // FAILURE-ATOMIC: every new buffer is allocated and filled through locals; the handle is touched only once all of that has succeeded.
   // A failed re-bind (out of device memory on a grown mesh) leaves the handle exactly as it was -- old mesh, old tables, still usable.
-  int* nvi = nullptr;
-  int* nci = nullptr;
-  double* nwork = nullptr;
+  DeviceBuffer<int> nvi, nci;
+  DeviceBuffer<double> nwork;
   int cap = h->cap_seg;
   const bool grow = nseg > h->cap_seg;
-  auto undo = [&](hipError_t e, const char* what) {
-    if (grow) { if (nvi) (void)hipFree(nvi); if (nci) (void)hipFree(nci); if (nwork) (void)hipFree(nwork); }
-    return hipfail(e, what);
-  };
-  hipError_t e;
   if (grow) {                                                    // grow: index tables, workspace, block staging
     cap = h->cap_seg > 0 ? std::max(nseg, h->cap_seg + h->cap_seg / 4) : nseg;   // (re-meshing grows by steps)
-    if ((e = hipMalloc(&nvi, size_t(ke->ir) * cap * sizeof(int))) != hipSuccess) return undo(e, "hipMalloc(vindex)");
-    if ((e = hipMalloc(&nci, size_t(ke->orr) * cap * sizeof(int))) != hipSuccess) return undo(e, "hipMalloc(cindex)");
+    HIP_TRY_AS(nvi.allocate(size_t(ke->ir) * cap), "hipMalloc(vindex)");
+    HIP_TRY_AS(nci.allocate(size_t(ke->orr) * cap), "hipMalloc(cindex)");
     if (ke->work_doubles) {
-      if ((e = hipMalloc(&nwork, size_t(cap) * ke->work_doubles * sizeof(double))) != hipSuccess) return undo(e, "hipMalloc(workspace)");
+      HIP_TRY_AS(nwork.allocate(size_t(cap) * ke->work_doubles), "hipMalloc(workspace)");
       // sections no kernel writes must read as zero (the interior-point sections of a Trapezoidal slot, defect_dims.h)
-      if ((e = hipMemset(nwork, 0, size_t(cap) * ke->work_doubles * sizeof(double))) != hipSuccess) return undo(e, "hipMemset(workspace)");
+      HIP_TRY_AS(hipMemset(nwork.get(), 0, size_t(cap) * ke->work_doubles * sizeof(double)), "hipMemset(workspace)");
     }
-  } else {
-    nvi = h->d_vindex, nci = h->d_cindex;
   }
   // (when the mesh still fits the kept tables are overwritten in place: both streams were drained above, and a failed copy into them
   //  poisons the handle -- nseg = 0 -- instead of leaving half-written tables behind an old segment count)
-  if ((e = hipMemcpy(nvi, vindex, nv * sizeof(int), hipMemcpyHostToDevice)) != hipSuccess) { if (!grow) h->nseg = 0; return undo(e, "hipMemcpy(vindex)"); }
-  if ((e = hipMemcpy(nci, cindex, nc * sizeof(int), hipMemcpyHostToDevice)) != hipSuccess) { if (!grow) h->nseg = 0; return undo(e, "hipMemcpy(cindex)"); }
-  if (grow) {
-    drop(h->d_vindex), drop(h->d_cindex), drop(h->d_work), drop(h->d_fx), drop(h->d_agx), drop(h->d_kkt);
-    h->d_vindex = nvi, h->d_cindex = nci, h->d_work = nwork, h->cap_seg = cap;
+  hipError_t e;
+  if ((e = hipMemcpy(grow ? nvi.get() : h->mesh.vindex.get(), vindex, nv * sizeof(int), hipMemcpyHostToDevice)) != hipSuccess) {
+    if (!grow) h->nseg = 0;
+    return hipfail(e, "hipMemcpy(vindex)");
   }
-  if (n_primal > h->cap_primal) drop(h->d_X), h->cap_primal = n_primal;
-  if (n_equal > h->cap_equal) drop(h->d_L), h->cap_equal = n_equal;
-  h->h_vindex.assign(vindex, vindex + nv);
-  h->h_cindex.assign(cindex, cindex + nc);
+  if ((e = hipMemcpy(grow ? nci.get() : h->mesh.cindex.get(), cindex, nc * sizeof(int), hipMemcpyHostToDevice)) != hipSuccess) {
+    if (!grow) h->nseg = 0;
+    return hipfail(e, "hipMemcpy(cindex)");
+  }
+  if (grow) {
+    h->mesh.vindex = std::move(nvi), h->mesh.cindex = std::move(nci), h->mesh.work = std::move(nwork), h->cap_seg = cap;
+    h->staging.fx = {}, h->staging.agx = {}, h->staging.kkt = {};
+  }
+  if (n_primal > h->cap_primal) h->staging.X = {}, h->cap_primal = n_primal;
+  if (n_equal > h->cap_equal) h->staging.L = {}, h->cap_equal = n_equal;
+  asset_hip_defect::MeshTables& m = h->mesh;
+  m.h_vindex.assign(vindex, vindex + nv);
+  m.h_cindex.assign(cindex, cindex + nc);
   {   // rows that are runs with a constant stride between applications (EvalArgs::affine)
     const int ir = ke->ir, orr = ke->orr, ns = nseg;
     const int v0 = vindex[0], c0 = cindex[0];
@@ -461,15 +486,10 @@ static int bind_tables(asset_hip_defect_t h, int nseg, const int32_t* vindex, co
       for (int k = 0; k < ir && ok; k++) ok = vindex[size_t(s) * ir + k] == v0 + s * vs + k;
       for (int k = 0; k < orr && ok; k++) ok = cindex[size_t(s) * orr + k] == c0 + s * cs + k;
     }
-    h->affine = ok ? 1 : 0, h->aff_v0 = v0, h->aff_vs = vs, h->aff_c0 = c0, h->aff_cs = cs;
+    m.affine = ok ? 1 : 0, m.aff_v0 = v0, m.aff_vs = vs, m.aff_c0 = c0, m.aff_cs = cs;
   }
-  // derived from the old tables: the KKT map and its staging, the RHS gather tables, per-application constants, block buffers
-  drop(h->d_map), drop(h->d_values), drop(h->d_stage), drop(h->d_multi_ptr), drop(h->d_multi_loc), drop(h->d_aconst);
-  drop(h->d_fx_rows), drop(h->d_fx_ptr), drop(h->d_fx_src), drop(h->d_gx_rows), drop(h->d_gx_ptr), drop(h->d_gx_src);
-  drop(h->d_fxb), drop(h->d_agxb);
-  if (h->h_values) { (void)hipHostFree(h->h_values); h->h_values = nullptr; }
-  h->map_len = 0, h->value_lo = h->value_hi = h->nvalues = 0, h->nmulti = 0, h->nstage = 0;
-  h->n_fx_rows = h->fx_long_from = h->n_gx_rows = h->gx_long_from = 0, h->rhs_tables_ready = false;
+  // derived from the old tables: the KKT map and its staging, the RHS gather tables and block buffers, per-application constants
+  h->kmap = {}, h->rhs = {}, h->aconst = {};
   h->nseg = nseg, h->n_primal = n_primal, h->n_equal = n_equal;
   return 0;
 }
@@ -487,56 +507,35 @@ int asset_hip_defect_create(const asset_hip_defect_desc* d, asset_hip_defect_t* 
     return fail(ASSET_HIP_ENOODE, buf);
   }
   if (ke->table->meta[asset_hip::MF_KIND] == 3) return fail(ASSET_HIP_EINVAL, "a bundle is launched through asset_hip_bundle_*, it is not a function");
-  {   // (before anything is allocated: the commonest set-up error)
-    const size_t nv = size_t(ke->ir) * d->nseg, nc = size_t(ke->orr) * d->nseg;
-    for (size_t i = 0; i < nv; i++)
-      if (d->vindex[i] < 0 || d->vindex[i] >= d->n_primal) return fail(ASSET_HIP_ERANGE, "vindex entry out of range");
-    for (size_t i = 0; i < nc; i++)
-      if (d->cindex[i] < 0 || d->cindex[i] >= d->n_equal) return fail(ASSET_HIP_ERANGE, "cindex entry out of range");
-  }
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-    return fail(ASSET_HIP_ENODEV, "no HIP device visible: the evaluator has no CPU fallback");
-  if (d->device < 0 || d->device >= ndev) return fail(ASSET_HIP_EINVAL, "device ordinal out of range");
-  HIP_TRY(hipSetDevice(d->device));
-  asset_hip_defect* h = new (std::nothrow) asset_hip_defect;
+  // (before anything is allocated: the commonest set-up error)
+  if (const int rc = check_index_tables(ke, d->nseg, d->vindex, d->cindex, d->n_primal, d->n_equal)) return rc;
+  if (const int rc = use_device(d->device, "no HIP device visible: the evaluator has no CPU fallback")) return rc;
+  // (a failing path below returns: the handle goes as asset_hip_defect_destroy lets it go)
+  std::unique_ptr<asset_hip_defect, void (*)(asset_hip_defect_t)> h(new (std::nothrow) asset_hip_defect, asset_hip_defect_destroy);
   if (!h) return fail(ASSET_HIP_EINVAL, "out of host memory");
   h->ke = ke, h->device = d->device;
   hipDeviceProp_t prop;
-  hipError_t e = hipGetDeviceProperties(&prop, d->device);
-  const int cus = (e == hipSuccess && prop.multiProcessorCount > 0) ? prop.multiProcessorCount : 256;
-  h->cus = cus;
-  auto bail = [&](hipError_t err, const char* w) {
-    int rc = hipfail(err, w);
-    asset_hip_defect_destroy(h);
-    return rc;
-  };
-  if ((e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking)) != hipSuccess) return bail(e, "hipStreamCreate");
-  {
-    const int rc = bind_tables(h, d->nseg, d->vindex, d->cindex, d->n_primal, d->n_equal);
-    if (rc) {
-      asset_hip_defect_destroy(h);
-      return rc;
-    }
-  }
+  const hipError_t e = hipGetDeviceProperties(&prop, d->device);
+  h->cus = (e == hipSuccess && prop.multiProcessorCount > 0) ? prop.multiProcessorCount : 256;
+  HIP_TRY_AS(h->stream.create(), "hipStreamCreate");
+  if (const int rc = bind_tables(h.get(), d->nseg, d->vindex, d->cindex, d->n_primal, d->n_equal)) return rc;
   // per-lane constants of the dense stage: computed here, once
-    for (int level = 0; level <= 2; level++) {   // (0: the record of the resident kernel)
-      const size_t nb = asset_hip::entry_lane_bytes(ke, level);
-      if (!nb) continue;
-      // ASSET_LANE_REPLICAS copies: every workgroup of the dense stage loads the whole table when it starts, all at the
-      // same moment -- with one copy that is thousands of requests for the same few hundred cache lines, which the L2
-      // channels holding them serve one after the other; workgroup b reads copy b % ASSET_LANE_REPLICAS.
-      if ((e = hipMalloc(&h->d_lane[level], nb * ASSET_LANE_REPLICAS)) != hipSuccess) return bail(e, "hipMalloc(lane constants)");
-      if ((e = asset_hip::entry_lane_setup(ke, level, h->d_lane[level], h->stream)) != hipSuccess) return bail(e, "lane_setup_kernel");
-      for (int r = 1; r < ASSET_LANE_REPLICAS; r++)
-        if ((e = hipMemcpyAsync(static_cast<char*>(h->d_lane[level]) + size_t(r) * nb, h->d_lane[level], nb,
-                                hipMemcpyDeviceToDevice, h->stream)) != hipSuccess)
-          return bail(e, "hipMemcpy(lane constants)");
-    }
-  if ((e = hipStreamSynchronize(h->stream)) != hipSuccess) return bail(e, "lane_setup_kernel");
-  if ((e = hipEventCreate(&h->ev0)) != hipSuccess) return bail(e, "hipEventCreate");
-  if ((e = hipEventCreate(&h->ev1)) != hipSuccess) return bail(e, "hipEventCreate");
-  *out = h;
+  for (int level = 0; level <= 2; level++) {   // (0: the record of the resident kernel)
+    const size_t nb = asset_hip::entry_lane_bytes(ke, level);
+    if (!nb) continue;
+    // ASSET_LANE_REPLICAS copies: every workgroup of the dense stage loads the whole table when it starts, all at the
+    // same moment -- with one copy that is thousands of requests for the same few hundred cache lines, which the L2
+    // channels holding them serve one after the other; workgroup b reads copy b % ASSET_LANE_REPLICAS.
+    HIP_TRY_AS(h->lane[level].allocate(nb * ASSET_LANE_REPLICAS), "hipMalloc(lane constants)");
+    char* lane = h->lane[level].get();
+    HIP_TRY_AS(asset_hip::entry_lane_setup(ke, level, lane, h->stream.get()), "lane_setup_kernel");
+    for (int r = 1; r < ASSET_LANE_REPLICAS; r++)
+      HIP_TRY_AS(hipMemcpyAsync(lane + size_t(r) * nb, lane, nb, hipMemcpyDeviceToDevice, h->stream.get()), "hipMemcpy(lane constants)");
+  }
+  HIP_TRY_AS(hipStreamSynchronize(h->stream.get()), "lane_setup_kernel");
+  HIP_TRY_AS(h->ev0.create(), "hipEventCreate");
+  HIP_TRY_AS(h->ev1.create(), "hipEventCreate");
+  *out = h.release();
   return 0;
 }
 
@@ -544,6 +543,7 @@ int asset_hip_defect_rebind(asset_hip_defect_t h, int nseg, const int32_t* vinde
   if (!h || !vindex || !cindex || nseg <= 0 || n_primal <= 0 || n_equal <= 0) return fail(ASSET_HIP_EINVAL, "bad rebind arguments");
   if (h->bundles > 0) return fail(ASSET_HIP_EINVAL, "the handle is a member of a bundle: destroy the bundle before re-binding");
   HIP_TRY(hipSetDevice(h->device));
+  if (const int rc = check_index_tables(h->ke, nseg, vindex, cindex, n_primal, n_equal)) return rc;
   return bind_tables(h, nseg, vindex, cindex, n_primal, n_equal);
 }
 
@@ -554,17 +554,7 @@ void asset_hip_defect_destroy(asset_hip_defect_t h) {
     return;
   }
   (void)hipSetDevice(h->device);
-  if (h->stream) (void)hipStreamSynchronize(h->stream);
-  for (void* p : {(void*)h->d_vindex, (void*)h->d_cindex, (void*)h->d_X, (void*)h->d_L, (void*)h->d_fx,
-                  (void*)h->d_agx, (void*)h->d_kkt, (void*)h->d_work, (void*)h->d_map, (void*)h->d_values, (void*)h->d_aconst,
-                  (void*)h->d_stage, (void*)h->d_multi_ptr, (void*)h->d_multi_loc, (void*)h->d_fx_rows, (void*)h->d_fx_ptr,
-                  (void*)h->d_fx_src, (void*)h->d_gx_rows, (void*)h->d_gx_ptr, (void*)h->d_gx_src, (void*)h->d_fxb, (void*)h->d_agxb,
-                  h->d_lane[0], h->d_lane[1], h->d_lane[2]})
-    if (p) (void)hipFree(p);
-  if (h->h_values) (void)hipHostFree(h->h_values);
-  if (h->ev0) (void)hipEventDestroy(h->ev0);
-  if (h->ev1) (void)hipEventDestroy(h->ev1);
-  if (h->stream) (void)hipStreamDestroy(h->stream);
+  if (h->stream.get()) (void)hipStreamSynchronize(h->stream.get());
   delete h;
 }
 
@@ -631,7 +621,7 @@ int asset_hip_launch_plan_query(const char* ode, int mode, int blocked, int what
 }
 int asset_hip_defect_launch_plan(asset_hip_defect_t h, int what, int assembled, asset_hip_launch_plan* out) {
   if (!h) return fail(ASSET_HIP_EINVAL, "null handle");
-  return entry_launch_plan(h->ke, what, assembled, h->nseg, h->cus, h->d_lane[0] != nullptr, out);
+  return entry_launch_plan(h->ke, what, assembled, h->nseg, h->cus, bool(h->lane[0]), out);
 }
 const char* asset_hip_kernel_slot_name(int slot) { return asset_hip::kslot_name(slot); }
 int asset_hip_kernel_slot_kinds(int slot) {
@@ -656,42 +646,43 @@ static int fill_args(asset_hip_defect_t h, int what, const double* dX, const dou
   const bool keep_pays = h->ke->ir >= 64 || size_t(h->nseg) * size_t(h->ke->kstride) * sizeof(double) <= (size_t(192) << 20);
   a.flags = ((opts & ASSET_HIP_KEEP_HESSIAN_SLOTS) && keep_pays) ? 1 : 0;
   if (!dX) return fail(ASSET_HIP_EINVAL, "X is null");
-  const bool needs_l = (what == ASSET_HIP_CON_ADJGRAD || what == ASSET_HIP_JAC_ADJGRAD || what == ASSET_HIP_JAC_ADJGRAD_HESS);
+  const bool needs_l = wants_multipliers(what);
   if (needs_l && !dL) return fail(ASSET_HIP_EINVAL, "L is null for an evaluation kind that contracts with multipliers");
   a.nseg = h->nseg;
   a.X = dX;
   a.L = needs_l ? dL : nullptr;
-  a.vindex = h->d_vindex;
-  a.cindex = h->d_cindex;
+  const asset_hip_defect::MeshTables& m = h->mesh;
+  a.vindex = m.vindex.get();
+  a.cindex = m.cindex.get();
   a.FX = dfx;
-  a.AGX = (what == ASSET_HIP_CON || what == ASSET_HIP_JAC) ? nullptr : dagx;
-  a.KKT = (what >= ASSET_HIP_JAC) ? dkkt : nullptr;
-  a.work = h->d_work;
-  a.lane_consts = level >= 1 ? h->d_lane[level] : nullptr;
-  a.lane_consts_res = h->d_lane[0];
-  a.affine = asset_hip::tuning().no_affine ? 0 : h->affine, a.aff_v0 = h->aff_v0, a.aff_vs = h->aff_vs, a.aff_c0 = h->aff_c0, a.aff_cs = h->aff_cs;
-  a.appl_consts = h->d_aconst;
-  if (h->ke->naconst > 0 && !h->d_aconst)
+  a.AGX = needs_l ? dagx : nullptr;
+  a.KKT = wants_kkt(what) ? dkkt : nullptr;
+  a.work = m.work.get();
+  a.lane_consts = level >= 1 ? h->lane[level].get() : nullptr;
+  a.lane_consts_res = h->lane[0].get();
+  a.affine = asset_hip::tuning().no_affine ? 0 : m.affine, a.aff_v0 = m.aff_v0, a.aff_vs = m.aff_vs, a.aff_c0 = m.aff_c0, a.aff_cs = m.aff_cs;
+  a.appl_consts = h->aconst.get();
+  if (h->ke->naconst > 0 && !h->aconst)
     return fail(ASSET_HIP_EINVAL, "this function reads constants of its applications: call asset_hip_defect_set_appl_consts first");
   return 0;
 }
 
 static int launch(asset_hip_defect_t h, int what, const double* dX, const double* dL, double* dfx, double* dagx,
                   double* dkkt, hipStream_t st, double* d_values = nullptr) {
-  if (st != h->stream) h->last_stream = st, h->last_stream_used = true;
+  if (st != h->stream.get()) h->last_stream = st, h->last_stream_used = true;
   asset_hip::EvalArgs a;
   const int rc = fill_args(h, what, dX, dL, dfx, dagx, dkkt, a);
   if (rc) return rc;
   const int level = level_of(what);
   if (d_values) {                                                          // on-device assembly
-    a.kmap = h->d_map, a.values = d_values, a.KKT = nullptr;
-    a.stage = h->d_stage, a.nvalues = int(h->nvalues);
+    a.kmap = h->kmap.map.get(), a.values = d_values, a.KKT = nullptr;
+    a.stage = h->kmap.stage.get(), a.nvalues = int(h->kmap.nvalues);
   }
   hipError_t e = asset_hip::entry_launch(h->ke, level, a, h->cus, st);
   if (e != hipSuccess) return hipfail(e, "kernel launch");
-  if (d_values && h->nmulti > 0 && level >= 2) {   // the staged locations (Hessian entries only): fixed-order sums
-    hipLaunchKernelGGL(asset_hip::asm_reduce_kernel, dim3(h->nmulti), dim3(256), 0, st, d_values, h->d_stage, h->d_multi_ptr,
-                       h->d_multi_loc);
+  if (d_values && h->kmap.multi_loc && level >= 2) {   // the staged locations (Hessian entries only): fixed-order sums
+    hipLaunchKernelGGL(asset_hip::asm_reduce_kernel, dim3(unsigned(h->kmap.multi_loc.size())), dim3(256), 0, st, d_values, h->kmap.stage.get(),
+                       h->kmap.multi_ptr.get(), h->kmap.multi_loc.get());
     if ((e = hipGetLastError()) != hipSuccess) return hipfail(e, "asm_reduce_kernel");
   }
   return 0;
@@ -701,7 +692,7 @@ int asset_hip_defect_eval_device(asset_hip_defect_t h, int what, const double* d
                                  double* dagx, double* dkkt, void* stream) {
   if (!h) return fail(ASSET_HIP_EINVAL, "null handle");
   HIP_TRY(hipSetDevice(h->device));
-  return launch(h, what, dX, dL, dfx, dagx, dkkt, stream ? static_cast<hipStream_t>(stream) : h->stream);
+  return launch(h, what, dX, dL, dfx, dagx, dkkt, stream_or(h, stream));
 }
 
 // ---- bundles: several plain functions in one launch (func_kernels.h: func_bundle_kernel) ---------------------------------
@@ -764,7 +755,7 @@ int asset_hip_bundle_eval_device(asset_hip_bundle_t b, int what, const double* d
   }
   for (int k = n; k <= asset_hip::BUNDLE_MAX; k++) args.start[k] = blocks;
   void* kargs[] = {&args};
-  hipStream_t st = stream ? static_cast<hipStream_t>(stream) : b->members[0]->stream;
+  hipStream_t st = stream_or(b->members[0], stream);
   const int slot = level == 0 ? asset_hip::K_BUNDLE0 : (level == 1 ? asset_hip::K_BUNDLE1 : asset_hip::K_BUNDLE2);
   hipError_t e = asset_hip::klaunch(b->ke->table->k[slot], dim3(blocks), dim3(64), shmem, st, kargs);
   if (e != hipSuccess) return hipfail(e, "bundle launch");
@@ -775,20 +766,35 @@ int asset_hip_defect_time_device(asset_hip_defect_t h, int what, const double* d
                                  double* dagx, double* dkkt, int warmup, int iters, float* ms_per_launch) {
   if (!h || !ms_per_launch || iters <= 0) return fail(ASSET_HIP_EINVAL, "bad timing arguments");
   HIP_TRY(hipSetDevice(h->device));
+  hipStream_t st = h->stream.get();
   for (int i = 0; i < warmup; i++) {
-    int rc = launch(h, what, dX, dL, dfx, dagx, dkkt, h->stream);
+    int rc = launch(h, what, dX, dL, dfx, dagx, dkkt, st);
     if (rc) return rc;
   }
-  HIP_TRY(hipEventRecord(h->ev0, h->stream));
+  HIP_TRY(hipEventRecord(h->ev0.get(), st));
   for (int i = 0; i < iters; i++) {
-    int rc = launch(h, what, dX, dL, dfx, dagx, dkkt, h->stream);
+    int rc = launch(h, what, dX, dL, dfx, dagx, dkkt, st);
     if (rc) return rc;
   }
-  HIP_TRY(hipEventRecord(h->ev1, h->stream));
-  HIP_TRY(hipEventSynchronize(h->ev1));
+  HIP_TRY(hipEventRecord(h->ev1.get(), st));
+  HIP_TRY(hipEventSynchronize(h->ev1.get()));
   float ms = 0.f;
-  HIP_TRY(hipEventElapsedTime(&ms, h->ev0, h->ev1));
+  HIP_TRY(hipEventElapsedTime(&ms, h->ev0.get(), h->ev1.get()));
   *ms_per_launch = ms / float(iters);
+  return 0;
+}
+
+// The staging of the host-pointer entry points: allocated on first use, sized for the handle's capacity (asset_hip_defect_rebind
+// keeps it while the new mesh fits); X and L copied in on the handle's stream
+static int stage_inputs(asset_hip_defect_t h, const double* X, const double* L, bool fx, bool agx, bool kkt) {
+  asset_hip_defect::HostStaging& s = h->staging;
+  if (!s.X) HIP_TRY(s.X.allocate(h->cap_primal));
+  if (!s.L) HIP_TRY(s.L.allocate(h->cap_equal));
+  if (fx && !s.fx) HIP_TRY(s.fx.allocate(size_t(h->cap_seg) * h->ke->orr));
+  if (agx && !s.agx) HIP_TRY(s.agx.allocate(size_t(h->cap_seg) * h->ke->ir));
+  if (kkt && !s.kkt) HIP_TRY(s.kkt.allocate(size_t(h->cap_seg) * h->ke->kstride));
+  HIP_TRY(hipMemcpyAsync(s.X.get(), X, sizeof(double) * h->n_primal, hipMemcpyHostToDevice, h->stream.get()));
+  if (L) HIP_TRY(hipMemcpyAsync(s.L.get(), L, sizeof(double) * h->n_equal, hipMemcpyHostToDevice, h->stream.get()));
   return 0;
 }
 
@@ -799,24 +805,18 @@ int asset_hip_defect_eval(asset_hip_defect_t h, int what, const double* X, const
   HIP_TRY(hipSetDevice(h->device));
   const size_t nfx = size_t(h->nseg) * h->ke->orr, nagx = size_t(h->nseg) * h->ke->ir,
                nkkt = size_t(h->nseg) * h->ke->kstride;   // (blocks in the handle's layout: asset_hip_defect_kkt_layout)
-  if (!h->d_X) HIP_TRY(hipMalloc(&h->d_X, sizeof(double) * h->cap_primal));
-  if (!h->d_L) HIP_TRY(hipMalloc(&h->d_L, sizeof(double) * h->cap_equal));
-  if (fx && !h->d_fx) HIP_TRY(hipMalloc(&h->d_fx, sizeof(double) * size_t(h->cap_seg) * h->ke->orr));   // (sized for the handle's capacity: asset_hip_defect_rebind)
-  if (agx && !h->d_agx) HIP_TRY(hipMalloc(&h->d_agx, sizeof(double) * size_t(h->cap_seg) * h->ke->ir));
-  if (kkt && !h->d_kkt) HIP_TRY(hipMalloc(&h->d_kkt, sizeof(double) * size_t(h->cap_seg) * h->ke->kstride));
-  HIP_TRY(hipMemcpyAsync(h->d_X, X, sizeof(double) * h->n_primal, hipMemcpyHostToDevice, h->stream));
-  if (L) HIP_TRY(hipMemcpyAsync(h->d_L, L, sizeof(double) * h->n_equal, hipMemcpyHostToDevice, h->stream));
-  int rc = launch(h, what, h->d_X, L ? h->d_L : nullptr, fx ? h->d_fx : nullptr, agx ? h->d_agx : nullptr,
-                  kkt ? h->d_kkt : nullptr, h->stream);
+  int rc = stage_inputs(h, X, L, fx, agx, kkt);
+  if (rc) return rc;
+  const asset_hip_defect::HostStaging& s = h->staging;
+  hipStream_t st = h->stream.get();
+  rc = launch(h, what, s.X.get(), L ? s.L.get() : nullptr, fx ? s.fx.get() : nullptr, agx ? s.agx.get() : nullptr,
+              kkt ? s.kkt.get() : nullptr, st);
   if (rc) return rc;
   const int level = level_of(what);
-  what &= 0xff;
-  if (fx) HIP_TRY(hipMemcpyAsync(fx, h->d_fx, sizeof(double) * nfx, hipMemcpyDeviceToHost, h->stream));
-  if (agx && what != ASSET_HIP_CON && what != ASSET_HIP_JAC)
-    HIP_TRY(hipMemcpyAsync(agx, h->d_agx, sizeof(double) * nagx, hipMemcpyDeviceToHost, h->stream));
-  if (kkt && level >= 1 && what >= ASSET_HIP_JAC)
-    HIP_TRY(hipMemcpyAsync(kkt, h->d_kkt, sizeof(double) * nkkt, hipMemcpyDeviceToHost, h->stream));
-  HIP_TRY(hipStreamSynchronize(h->stream));
+  if (fx) HIP_TRY(hipMemcpyAsync(fx, s.fx.get(), sizeof(double) * nfx, hipMemcpyDeviceToHost, st));
+  if (agx && wants_multipliers(what)) HIP_TRY(hipMemcpyAsync(agx, s.agx.get(), sizeof(double) * nagx, hipMemcpyDeviceToHost, st));
+  if (kkt && level >= 1 && wants_kkt(what)) HIP_TRY(hipMemcpyAsync(kkt, s.kkt.get(), sizeof(double) * nkkt, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
   return 0;
 }
 
@@ -826,8 +826,8 @@ int asset_hip_defect_set_appl_consts(asset_hip_defect_t h, const double* consts,
     return fail(ASSET_HIP_EINVAL, "the number of constants per application does not match the function");
   HIP_TRY(hipSetDevice(h->device));
   const size_t n = size_t(h->nseg) * per_application;
-  if (!h->d_aconst) HIP_TRY(hipMalloc(&h->d_aconst, n * sizeof(double)));
-  HIP_TRY(hipMemcpy(h->d_aconst, consts, n * sizeof(double), hipMemcpyHostToDevice));
+  if (!h->aconst) HIP_TRY(h->aconst.allocate(n));
+  HIP_TRY(hipMemcpy(h->aconst.get(), consts, n * sizeof(double), hipMemcpyHostToDevice));
   return 0;
 }
 
@@ -855,19 +855,15 @@ int asset_hip_mesh_error_deboor(const char* ode, int mode, int blocked, const do
   const int nb = (nnodes - 1) / (cs - 1);
   if (nb < 2 || nb * (cs - 1) + 1 != nnodes)
     return fail(ASSET_HIP_EINVAL, "the trajectory must hold nb*(cs-1)+1 nodes with nb >= 2 blocks");
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-    return fail(ASSET_HIP_ENODEV, "no HIP device visible: the estimator has no CPU fallback");
-  if (device < 0 || device >= ndev) return fail(ASSET_HIP_EINVAL, "device ordinal out of range");
-  HIP_TRY(hipSetDevice(device));
+  if (const int rc = use_device(device, "no HIP device visible: the estimator has no CPU fallback")) return rc;
   // one allocation: traj | yvec | hs | tsnd | errors | dist | error_max | dist_max
   const size_t sz_traj = size_t(nnodes) * N, sz_y = size_t(nb) * n, sz_e = size_t(nb + 1) * n;
   const size_t total = sz_traj + sz_y + nb + (nb + 1) + 2 * sz_e + 2 * size_t(nb + 1);
-  double* buf = nullptr;
-  HIP_TRY(hipMalloc(&buf, total * sizeof(double)));
+  DeviceBuffer<double> buf;
+  HIP_TRY(buf.allocate(total));
   asset_hip::MeshArgs a;
   a.nb = nb;
-  double* p = buf;
+  double* p = buf.get();
   a.traj = p, p += sz_traj;
   a.yvec = p, p += sz_y;
   a.hs = p, p += nb;
@@ -876,19 +872,14 @@ int asset_hip_mesh_error_deboor(const char* ode, int mode, int blocked, const do
   a.dist = p, p += sz_e;
   a.error_max = p, p += nb + 1;
   a.dist_max = p;
-  auto done = [&](int rc) { (void)hipFree(buf); return rc; };
-  hipError_t e = hipMemcpy(buf, traj, sz_traj * sizeof(double), hipMemcpyHostToDevice);
-  if (e != hipSuccess) return done(hipfail(e, "hipMemcpy(traj)"));
-  if ((e = asset_hip::entry_mesh(ke, a, nullptr)) != hipSuccess) return done(hipfail(e, "mesh kernels"));
-  if ((e = hipMemcpy(tsnd, a.tsnd, (nb + 1) * sizeof(double), hipMemcpyDeviceToHost)) != hipSuccess ||
-      (e = hipMemcpy(mesh_errors, a.errors, sz_e * sizeof(double), hipMemcpyDeviceToHost)) != hipSuccess ||
-      (e = hipMemcpy(mesh_dist, a.dist, sz_e * sizeof(double), hipMemcpyDeviceToHost)) != hipSuccess)
-    return done(hipfail(e, "hipMemcpy(results)"));
-  if (error_max && (e = hipMemcpy(error_max, a.error_max, (nb + 1) * sizeof(double), hipMemcpyDeviceToHost)) != hipSuccess)
-    return done(hipfail(e, "hipMemcpy(error_max)"));
-  if (dist_max && (e = hipMemcpy(dist_max, a.dist_max, (nb + 1) * sizeof(double), hipMemcpyDeviceToHost)) != hipSuccess)
-    return done(hipfail(e, "hipMemcpy(dist_max)"));
-  return done(0);
+  HIP_TRY_AS(hipMemcpy(buf.get(), traj, sz_traj * sizeof(double), hipMemcpyHostToDevice), "hipMemcpy(traj)");
+  HIP_TRY_AS(asset_hip::entry_mesh(ke, a, nullptr), "mesh kernels");
+  HIP_TRY_AS(hipMemcpy(tsnd, a.tsnd, (nb + 1) * sizeof(double), hipMemcpyDeviceToHost), "hipMemcpy(results)");
+  HIP_TRY_AS(hipMemcpy(mesh_errors, a.errors, sz_e * sizeof(double), hipMemcpyDeviceToHost), "hipMemcpy(results)");
+  HIP_TRY_AS(hipMemcpy(mesh_dist, a.dist, sz_e * sizeof(double), hipMemcpyDeviceToHost), "hipMemcpy(results)");
+  if (error_max) HIP_TRY_AS(hipMemcpy(error_max, a.error_max, (nb + 1) * sizeof(double), hipMemcpyDeviceToHost), "hipMemcpy(error_max)");
+  if (dist_max) HIP_TRY_AS(hipMemcpy(dist_max, a.dist_max, (nb + 1) * sizeof(double), hipMemcpyDeviceToHost), "hipMemcpy(dist_max)");
+  return 0;
 }
 
 // ---------------------------------------------------------------------------------------------- trajectory table
@@ -897,13 +888,12 @@ struct asset_hip_traj_table {
   const asset_hip::KernelEntry* ke = nullptr;
   int nb = 0, nnodes = 0, N = 0, n = 0, device = 0, cus = 256;
   double t0 = 0.0, tf = 0.0;
-  double* d_buf = nullptr;     // traj | xdot | tb, resident
+  asset_hip::Stream stream;                 // (first: it goes after the buffers)
+  DeviceBuffer<double> buf;                 // traj | xdot | tb, resident
   asset_hip::InterpArgs a{};
-  // staging of the host-pointer entry point (grown on demand): times | out | dout, and the counter
-  double* d_stage = nullptr;
-  long long cap_q = 0;
-  unsigned long long* d_count = nullptr;
-  hipStream_t stream = nullptr;
+  // staging of the host-pointer entry point (grown on demand): times | out | dout for as many queries as fit, and the counter
+  DeviceBuffer<double> stage;
+  DeviceBuffer<unsigned long long> count;
 };
 
 int asset_hip_traj_table_create(const char* ode, int mode, int blocked, const double* traj, int nnodes, int device,
@@ -927,11 +917,7 @@ int asset_hip_traj_table_create(const char* ode, int mode, int blocked, const do
     if (d == 0.0) return fail(ASSET_HIP_EINVAL, "the trajectory holds duplicate times (node " + std::to_string(j) + ")");
     if ((d > 0.0) != (dirn > 0.0)) return fail(ASSET_HIP_EINVAL, "the trajectory's times are not monotonic (node " + std::to_string(j) + ")");
   }
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-    return fail(ASSET_HIP_ENODEV, "no HIP device visible: the trajectory table has no CPU fallback");
-  if (device < 0 || device >= ndev) return fail(ASSET_HIP_EINVAL, "device ordinal out of range");
-  HIP_TRY(hipSetDevice(device));
+  if (const int rc = use_device(device, "no HIP device visible: the trajectory table has no CPU fallback")) return rc;
   std::unique_ptr<asset_hip_traj_table> t(new (std::nothrow) asset_hip_traj_table());
   if (!t) return fail(ASSET_HIP_EINVAL, "out of host memory");
   t->ke = ke, t->nb = nb, t->nnodes = nnodes, t->N = N, t->n = n, t->device = device;
@@ -939,22 +925,14 @@ int asset_hip_traj_table_create(const char* ode, int mode, int blocked, const do
   hipDeviceProp_t prop;
   if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0) t->cus = prop.multiProcessorCount;
   const size_t sz_traj = size_t(nnodes) * N, sz_xd = size_t(nnodes) * n, total = sz_traj + sz_xd + size_t(nb) + 1;
-  auto bail = [&](int rc) {
-    if (t->d_buf) (void)hipFree(t->d_buf);
-    if (t->d_count) (void)hipFree(t->d_count);
-    if (t->stream) (void)hipStreamDestroy(t->stream);
-    return rc;
-  };
-  hipError_t e;
-  if ((e = hipStreamCreateWithFlags(&t->stream, hipStreamNonBlocking)) != hipSuccess) return bail(hipfail(e, "hipStreamCreate"));
-  if ((e = hipMalloc(&t->d_buf, total * sizeof(double))) != hipSuccess) return bail(hipfail(e, "hipMalloc(table)"));
-  if ((e = hipMalloc(&t->d_count, sizeof(unsigned long long))) != hipSuccess) return bail(hipfail(e, "hipMalloc(counter)"));
+  HIP_TRY_AS(t->stream.create(), "hipStreamCreate");
+  HIP_TRY_AS(t->buf.allocate(total), "hipMalloc(table)");
+  HIP_TRY_AS(t->count.allocate(1), "hipMalloc(counter)");
   t->a.nb = nb, t->a.nq = 0;
-  t->a.traj = t->d_buf, t->a.xdot = t->d_buf + sz_traj, t->a.tb = t->d_buf + sz_traj + sz_xd;
-  if ((e = hipMemcpyAsync(t->d_buf, traj, sz_traj * sizeof(double), hipMemcpyHostToDevice, t->stream)) != hipSuccess)
-    return bail(hipfail(e, "hipMemcpy(traj)"));
-  if ((e = asset_hip::entry_interp_table(ke, t->a, t->stream)) != hipSuccess) return bail(hipfail(e, "interp_xdot_kernel"));
-  if ((e = hipStreamSynchronize(t->stream)) != hipSuccess) return bail(hipfail(e, "trajectory table set-up"));
+  t->a.traj = t->buf.get(), t->a.xdot = t->buf.get() + sz_traj, t->a.tb = t->buf.get() + sz_traj + sz_xd;
+  HIP_TRY_AS(hipMemcpyAsync(t->buf.get(), traj, sz_traj * sizeof(double), hipMemcpyHostToDevice, t->stream.get()), "hipMemcpy(traj)");
+  HIP_TRY_AS(asset_hip::entry_interp_table(ke, t->a, t->stream.get()), "interp_xdot_kernel");
+  HIP_TRY_AS(hipStreamSynchronize(t->stream.get()), "trajectory table set-up");
   *out = t.release();
   return 0;
 }
@@ -973,7 +951,7 @@ int asset_hip_traj_table_interp_device(asset_hip_traj_table_t t, const double* d
   if (!t) return fail(ASSET_HIP_EINVAL, "null table");
   if (n < 0 || (n > 0 && (!d_times || !d_out)) || (deriv && n > 0 && !d_dout)) return fail(ASSET_HIP_EINVAL, "bad interpolation arguments");
   HIP_TRY(hipSetDevice(t->device));
-  return traj_table_launch(t, d_times, n, deriv, d_out, d_dout, d_n_outside, stream ? static_cast<hipStream_t>(stream) : t->stream);
+  return traj_table_launch(t, d_times, n, deriv, d_out, d_dout, d_n_outside, stream_or(t, stream));
 }
 
 int asset_hip_traj_table_interp(asset_hip_traj_table_t t, const double* times, long long n, int deriv, double* out, double* dout,
@@ -986,23 +964,22 @@ int asset_hip_traj_table_interp(asset_hip_traj_table_t t, const double* times, l
     if (!std::isfinite(times[i])) return fail(ASSET_HIP_EINVAL, "NaN or Inf among the query times");
   HIP_TRY(hipSetDevice(t->device));
   const size_t N = size_t(t->N);
-  if (n > t->cap_q) {   // times | out | dout
-    HIP_TRY(hipStreamSynchronize(t->stream));
-    if (t->d_stage) (void)hipFree(t->d_stage);
-    t->d_stage = nullptr, t->cap_q = 0;
-    HIP_TRY(hipMalloc(&t->d_stage, size_t(n) * (1 + 2 * N) * sizeof(double)));
-    t->cap_q = n;
+  hipStream_t st = t->stream.get();
+  if (size_t(n) * (1 + 2 * N) > t->stage.size()) {   // times | out | dout
+    HIP_TRY(hipStreamSynchronize(st));
+    HIP_TRY(t->stage.allocate(size_t(n) * (1 + 2 * N)));
   }
-  double *d_times = t->d_stage, *d_out = d_times + t->cap_q, *d_dout = d_out + size_t(t->cap_q) * N;
-  HIP_TRY(hipMemcpyAsync(d_times, times, size_t(n) * sizeof(double), hipMemcpyHostToDevice, t->stream));
-  HIP_TRY(hipMemsetAsync(t->d_count, 0, sizeof(unsigned long long), t->stream));
-  const int rc = traj_table_launch(t, d_times, n, deriv, d_out, d_dout, t->d_count, t->stream);
+  const size_t cap_q = t->stage.size() / (1 + 2 * N);
+  double *d_times = t->stage.get(), *d_out = d_times + cap_q, *d_dout = d_out + cap_q * N;
+  HIP_TRY(hipMemcpyAsync(d_times, times, size_t(n) * sizeof(double), hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemsetAsync(t->count.get(), 0, sizeof(unsigned long long), st));
+  const int rc = traj_table_launch(t, d_times, n, deriv, d_out, d_dout, t->count.get(), st);
   if (rc) return rc;
-  HIP_TRY(hipMemcpyAsync(out, d_out, size_t(n) * N * sizeof(double), hipMemcpyDeviceToHost, t->stream));
-  if (deriv) HIP_TRY(hipMemcpyAsync(dout, d_dout, size_t(n) * N * sizeof(double), hipMemcpyDeviceToHost, t->stream));
+  HIP_TRY(hipMemcpyAsync(out, d_out, size_t(n) * N * sizeof(double), hipMemcpyDeviceToHost, st));
+  if (deriv) HIP_TRY(hipMemcpyAsync(dout, d_dout, size_t(n) * N * sizeof(double), hipMemcpyDeviceToHost, st));
   unsigned long long cnt = 0;
-  HIP_TRY(hipMemcpyAsync(&cnt, t->d_count, sizeof cnt, hipMemcpyDeviceToHost, t->stream));
-  HIP_TRY(hipStreamSynchronize(t->stream));
+  HIP_TRY(hipMemcpyAsync(&cnt, t->count.get(), sizeof cnt, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
   if (n_outside) *n_outside = (long long)cnt;
   return 0;
 }
@@ -1019,149 +996,53 @@ int asset_hip_traj_table_info(asset_hip_traj_table_t t, int* nblocks, int* ncols
 void asset_hip_traj_table_destroy(asset_hip_traj_table_t t) {
   if (!t) return;
   (void)hipSetDevice(t->device);
-  if (t->stream) (void)hipStreamSynchronize(t->stream);
+  if (t->stream.get()) (void)hipStreamSynchronize(t->stream.get());
   (void)hipDeviceSynchronize();          // (queries enqueued on the caller's streams still read the table)
-  if (t->d_buf) (void)hipFree(t->d_buf);
-  if (t->d_stage) (void)hipFree(t->d_stage);
-  if (t->d_count) (void)hipFree(t->d_count);
-  if (t->stream) (void)hipStreamDestroy(t->stream);
   delete t;
 }
 
 // ---------------------------------------------------------------------------------------------- on-device assembly
 
+int asset_hip_kkt_map_query(int ir, int orr, int plain_function, int nseg, const int32_t* slot_locations, long long nvalues,
+                            int accumulate, long long* map_len, int32_t* map_words, int* nmulti, int32_t* multi_ptr,
+                            int32_t* multi_loc, long long* lo, long long* hi) {
+  if (ir <= 0 || orr <= 0 || nseg <= 0 || !slot_locations || nvalues <= 0) return fail(ASSET_HIP_EINVAL, "bad kkt map arguments");
+  asset_hip::KktMap m;
+  const char* err = nullptr;
+  if (const int rc = asset_hip::build_kkt_map(ir, orr, plain_function != 0, nseg, slot_locations, nvalues, accumulate, m, &err))
+    return fail(rc, err);
+  if (map_len) *map_len = (long long)m.words.size();
+  if (nmulti) *nmulti = int(m.multi_loc.size());
+  if (lo) *lo = m.lo;
+  if (hi) *hi = m.hi;
+  if (map_words) std::copy(m.words.begin(), m.words.end(), map_words);
+  if (multi_ptr) std::copy(m.multi_ptr.begin(), m.multi_ptr.end(), multi_ptr);
+  if (multi_loc) std::copy(m.multi_loc.begin(), m.multi_loc.end(), multi_loc);
+  return 0;
+}
+
 int asset_hip_defect_set_kkt_map(asset_hip_defect_t h, const int32_t* slot_locations, long long nvalues, int accumulate) {
   if (!h || !slot_locations || nvalues <= 0) return fail(ASSET_HIP_EINVAL, "bad kkt map arguments");
   HIP_TRY(hipSetDevice(h->device));
-  const size_t nslots = size_t(h->nseg) * h->ke->nkkt;
-  long long lo = nvalues, hi = 0;
-  for (size_t i = 0; i < nslots; i++) {
-    const long long m = slot_locations[i];
-    if (m == -1) continue;   // a slot the caller does not want (the Jacobian slots of an objective: Hessian only)
-    if (m < 0 || m >= nvalues) return fail(ASSET_HIP_ERANGE, "kkt slot location outside [0, nvalues) and not -1");
-    lo = m < lo ? m : lo;
-    hi = m + 1 > hi ? m + 1 : hi;
+  // FAILURE-ATOMIC: the old map is dropped first (two maps side by side would not fit at the sizes that matter), the new one is built
+  // and uploaded through locals and committed by the last statement.  A failed call leaves a handle with no map -- the assembled
+  // kinds refuse -- never part of one.
+  h->kmap = {};
+  asset_hip::KktMap m;
+  const char* err = nullptr;
+  if (const int rc = asset_hip::build_kkt_map(h->ke->ir, h->ke->orr, h->ke->mode == ASSET_HIP_FUNCTION, h->nseg, slot_locations, nvalues,
+                                              accumulate, m, &err))
+    return fail(rc, err);
+  asset_hip_defect::DeviceKktMap g;
+  g.value_lo = m.lo, g.value_hi = m.hi, g.nvalues = nvalues;
+  HIP_TRY_AS(upload(g.map, m.words), "uploading the kkt map");
+  if (!m.multi_loc.empty()) {   // staging cells and the reduction lists
+    HIP_TRY_AS(g.stage.allocate(size_t(m.multi_ptr.back())), "hipMalloc(kkt staging cells)");
+    HIP_TRY_AS(hipMemset(g.stage.get(), 0, g.stage.size() * sizeof(double)), "hipMemset(kkt staging cells)");
+    HIP_TRY_AS(upload(g.multi_ptr, m.multi_ptr), "uploading the kkt reduction lists");
+    HIP_TRY_AS(upload(g.multi_loc, m.multi_loc), "uploading the kkt reduction lists");
   }
-  if (hi <= lo) return fail(ASSET_HIP_EINVAL, "kkt map keeps no slot");
-  // a location used by exactly one slot is stored to; one that two slots share is added to atomically (two terms: the
-  // order cannot matter); one that three or more share is STAGED -- every such slot gets a cell of its own and the cells
-  // of a location are summed in slot order afterwards (encoding: defect_dims.h, EvalArgs::kmap / stage).  In accumulate
-  // mode every slot adds atomically into whatever the array holds.
-  std::vector<unsigned char> uses(accumulate ? 0 : size_t(hi - lo), 0);
-  if (!accumulate)
-    for (size_t i = 0; i < nslots; i++) {
-      if (slot_locations[i] < 0) continue;
-      unsigned char& u = uses[size_t(slot_locations[i] - lo)];
-      if (u < 3) u++;
-    }
-  // only Hessian slots are staged (a Jacobian slot's location belongs to one constraint row of one application; and the
-  // Jacobian-only evaluation kinds write no Hessian entry, so they must not leave cells half-filled)
-  const int IRk = h->ke->ir, ORk = h->ke->orr, NKk = h->ke->nkkt;
-  std::vector<unsigned char> is_h(NKk, 0);
-  for (int c = 0, k = 0; c < IRk; c++) {
-    for (int j = c; j < IRk; j++) is_h[k++] = 1;
-    k += ORk;
-  }
-  auto staged = [&](size_t i) {
-    const int32_t m = slot_locations[i];
-    return m >= 0 && is_h[i % size_t(NKk)] && uses[size_t(m - lo)] >= 3;
-  };
-  std::vector<int32_t> multi_loc, multi_ptr(1, 0);
-  std::unordered_map<int32_t, int> multi_of;           // location -> index in multi_loc
-  if (!accumulate) {
-    for (size_t i = 0; i < nslots; i++) {
-      const int32_t m = slot_locations[i];
-      if (staged(i) && multi_of.emplace(m, 0).second) multi_loc.push_back(m);
-    }
-    std::sort(multi_loc.begin(), multi_loc.end());
-    for (size_t l = 0; l < multi_loc.size(); l++) multi_of[multi_loc[l]] = int(l);
-    std::vector<int> cnt(multi_loc.size(), 0);
-    for (size_t i = 0; i < nslots; i++) {
-      if (staged(i)) cnt[multi_of[slot_locations[i]]]++;
-    }
-    multi_ptr.resize(multi_loc.size() + 1);
-    for (size_t l = 0; l < multi_loc.size(); l++) multi_ptr[l + 1] = multi_ptr[l] + cnt[l];
-    if (nvalues + (long long)multi_ptr.back() + 2 > 2147483647LL)
-      return fail(ASSET_HIP_ERANGE, "value array + staging cells exceed the 32-bit map range");
-  }
-  std::vector<int32_t> enc(nslots);                     // map word of every slot, slot order (cells are handed out in it)
-  {
-    std::vector<int> fill(multi_ptr.begin(), multi_ptr.end() - (multi_ptr.size() > 1 ? 1 : 0));
-    for (size_t i = 0; i < nslots; i++) {
-      const int32_t m = slot_locations[i];
-      if (m < 0) enc[i] = -1;
-      else if (accumulate) enc[i] = -(m + 2);
-      else {
-        const unsigned char u = uses[size_t(m - lo)];
-        if (u == 1) enc[i] = m;
-        else if (!staged(i) || !multi_of.count(m)) enc[i] = -(m + 2);   // (a location staged for its Hessian slots takes no other)
-        else enc[i] = -(int32_t(nvalues) + fill[multi_of[m]]++ + 2);
-      }
-    }
-  }
-  std::vector<int32_t> map;
-  if (h->ke->mode == ASSET_HIP_FUNCTION) {   // plain functions place their entries slot by slot (func_kernels.h)
-    map = enc;
-  } else {
-    // fragment order of the LGL dense stage (defect_kernels.h, ASM): for every segment (4*tiles) rows of 64 lanes;
-    // lane (lr = l & 15, lk = l >> 4), entry v of an accumulator tile is block column c = 16ct + lk + 4v and row
-    // r = 16rt + lr (H, lower-triangle tiles first, tix = rt(rt+1)/2 + ct) or defect row jr = 16jt + lr
-    // (J, tile ct*TJ + jt); -1 where that entry is no KKT slot.
-    const int IR = h->ke->ir, OR = h->ke->orr, NK = h->ke->nkkt;
-    const int TI = (IR + 15) / 16, TJ = (OR + 15) / 16, NTH = TI * (TI + 1) / 2, NF = (NTH + TI * TJ) * 4;
-    std::vector<int32_t> slot_of(size_t(NF) * 64, -1);
-    for (int l = 0; l < 64; l++) {
-      const int lr = l & 15, lk = l >> 4;
-      for (int ct = 0; ct < TI; ct++)
-        for (int v = 0; v < 4; v++) {
-          const int c = 16 * ct + lk + 4 * v;
-          if (c >= IR) continue;
-          const int cst = c * (IR + OR) - c * (c - 1) / 2;   // first slot of block column c
-          for (int rt = ct; rt < TI; rt++) {
-            const int r = 16 * rt + lr;
-            if (r < IR && r >= c) slot_of[size_t((rt * (rt + 1) / 2 + ct) * 4 + v) * 64 + l] = cst + (r - c);
-          }
-          for (int jt = 0; jt < TJ; jt++) {
-            const int jr = 16 * jt + lr;
-            if (jr < OR) slot_of[size_t((NTH + ct * TJ + jt) * 4 + v) * 64 + l] = cst + (IR - c) + jr;
-          }
-        }
-    }
-    map.resize(size_t(h->nseg) * NF * 64);
-    for (int V = 0; V < h->nseg; V++) {
-      const int32_t* loc = slot_locations + size_t(V) * NK;
-      int32_t* dst = map.data() + size_t(V) * NF * 64;
-      const int32_t* encV = enc.data() + size_t(V) * NK;
-      (void)loc;
-      for (size_t e = 0; e < size_t(NF) * 64; e++) dst[e] = slot_of[e] < 0 ? -1 : encV[slot_of[e]];
-    }
-  }
-  if (h->d_map && h->map_len != map.size()) {
-    (void)hipFree(h->d_map);
-    h->d_map = nullptr;
-  }
-  if (!h->d_map) HIP_TRY(hipMalloc(&h->d_map, map.size() * sizeof(int32_t)));
-  h->map_len = map.size();
-  HIP_TRY(hipMemcpy(h->d_map, map.data(), map.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-  if (h->d_values && (hi - lo) != (h->value_hi - h->value_lo)) {
-    (void)hipFree(h->d_values);
-    (void)hipHostFree(h->h_values);
-    h->d_values = nullptr, h->h_values = nullptr;
-  }
-  h->value_lo = lo, h->value_hi = hi, h->nvalues = nvalues;
-  // staging cells and the reduction lists
-  for (void* p : {(void*)h->d_stage, (void*)h->d_multi_ptr, (void*)h->d_multi_loc})
-    if (p) (void)hipFree(p);
-  h->d_stage = nullptr, h->d_multi_ptr = h->d_multi_loc = nullptr;
-  h->nmulti = int(multi_loc.size()), h->nstage = size_t(multi_ptr.back());
-  if (h->nmulti > 0) {
-    HIP_TRY(hipMalloc(&h->d_stage, h->nstage * sizeof(double)));
-    HIP_TRY(hipMemset(h->d_stage, 0, h->nstage * sizeof(double)));
-    HIP_TRY(hipMalloc(&h->d_multi_ptr, multi_ptr.size() * sizeof(int)));
-    HIP_TRY(hipMalloc(&h->d_multi_loc, multi_loc.size() * sizeof(int)));
-    HIP_TRY(hipMemcpy(h->d_multi_ptr, multi_ptr.data(), multi_ptr.size() * sizeof(int), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(h->d_multi_loc, multi_loc.data(), multi_loc.size() * sizeof(int), hipMemcpyHostToDevice));
-  }
+  h->kmap = std::move(g);
   return 0;
 }
 
@@ -1171,12 +1052,11 @@ int asset_hip_defect_eval_assembled_device(asset_hip_defect_t h, int what, const
   what &= 0xff;   // (no blocks are written: ASSET_HIP_KEEP_HESSIAN_SLOTS has nothing to act on)
   if (!h) return fail(ASSET_HIP_EINVAL, "null handle");
   if (what < ASSET_HIP_JAC) return fail(ASSET_HIP_EINVAL, "assembled evaluation needs a kind that produces KKT entries");
-  if (!h->d_map) return fail(ASSET_HIP_EINVAL, "no kkt map: call asset_hip_defect_set_kkt_map first");
+  if (!h->kmap.map) return fail(ASSET_HIP_EINVAL, "no kkt map: call asset_hip_defect_set_kkt_map first");
   if (!d_kkt_values) return fail(ASSET_HIP_EINVAL, "kkt value array is null");
   HIP_TRY(hipSetDevice(h->device));
-  hipStream_t st = stream ? static_cast<hipStream_t>(stream) : h->stream;
   // the dense stage places its accumulators in the value array itself (defect_kernels.h, ASM instantiations)
-  return launch(h, what, dX, dL, d_fx_blocks, d_agx_blocks, nullptr, st, d_kkt_values);
+  return launch(h, what, dX, dL, d_fx_blocks, d_agx_blocks, nullptr, stream_or(h, stream), d_kkt_values);
 }
 
 // CSR by target row over the entries of a block array ([nseg][width], entry e = V * width + i goes to row index[e]):
@@ -1208,51 +1088,37 @@ static int build_rhs_csr(const std::vector<int32_t>& index, std::vector<int>& ro
   return long_from;
 }
 
+// the gather tables of a handle's index tables and the block buffers they read
+static hipError_t build_rhs_tables(const asset_hip_defect* h, asset_hip_defect::RhsTables& r) {
+  std::vector<int> rows, ptr, src;
+  hipError_t e;
+  r.fx_long_from = build_rhs_csr(h->mesh.h_cindex, rows, ptr, src);
+  r.n_fx_rows = int(rows.size());
+  if ((e = upload(r.fx_rows, rows, 1)) != hipSuccess || (e = upload(r.fx_ptr, ptr, 1)) != hipSuccess || (e = upload(r.fx_src, src, 1)) != hipSuccess) return e;
+  r.gx_long_from = build_rhs_csr(h->mesh.h_vindex, rows, ptr, src);
+  r.n_gx_rows = int(rows.size());
+  if ((e = upload(r.gx_rows, rows, 1)) != hipSuccess || (e = upload(r.gx_ptr, ptr, 1)) != hipSuccess || (e = upload(r.gx_src, src, 1)) != hipSuccess) return e;
+  if ((e = r.fxb.allocate(size_t(h->nseg) * h->ke->orr)) != hipSuccess) return e;
+  return r.agxb.allocate(size_t(h->nseg) * h->ke->ir);
+}
+
 int asset_hip_defect_eval_kkt_device(asset_hip_defect_t h, int what, const double* dX, const double* dL, double* d_FXE,
                                      double* d_AGX, double* d_kkt_values, void* stream) {
   what &= 0xff;   // (no blocks are written: ASSET_HIP_KEEP_HESSIAN_SLOTS has nothing to act on)
   if (!h) return fail(ASSET_HIP_EINVAL, "null handle");
   if (!d_FXE) return fail(ASSET_HIP_EINVAL, "FXE is null");
-  const bool want_kkt = what >= ASSET_HIP_JAC;
-  const bool want_agx = (what == ASSET_HIP_CON_ADJGRAD || what == ASSET_HIP_JAC_ADJGRAD || what == ASSET_HIP_JAC_ADJGRAD_HESS);
-  if (want_kkt && (!h->d_map || !d_kkt_values)) return fail(ASSET_HIP_EINVAL, "no kkt map / value array for a kind that fills the matrix");
+  const bool want_kkt = wants_kkt(what), want_agx = wants_multipliers(what);
+  if (want_kkt && (!h->kmap.map || !d_kkt_values)) return fail(ASSET_HIP_EINVAL, "no kkt map / value array for a kind that fills the matrix");
   if (want_agx && !d_AGX) return fail(ASSET_HIP_EINVAL, "AGX is null for a kind that produces the adjoint gradient");
   HIP_TRY(hipSetDevice(h->device));
-  hipStream_t st = stream ? static_cast<hipStream_t>(stream) : h->stream;
-  const int IR = h->ke->ir, OR = h->ke->orr;
-  if (!h->rhs_tables_ready) {   // the gather tables, once per handle: built into locals, committed only when all of them exist
-    int* d[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    double *fxb = nullptr, *agxb = nullptr;
-    int n_fx = 0, n_gx = 0, fx_long = 0, gx_long = 0;
-    auto build = [&]() -> hipError_t {
-      std::vector<int> rows, ptr, src;
-      auto up = [&](int*& dst, const std::vector<int>& v) -> hipError_t {
-        hipError_t e = hipMalloc(&dst, (v.size() + 1) * sizeof(int));
-        return e != hipSuccess ? e : hipMemcpy(dst, v.data(), v.size() * sizeof(int), hipMemcpyHostToDevice);
-      };
-      hipError_t e;
-      fx_long = build_rhs_csr(h->h_cindex, rows, ptr, src);
-      n_fx = int(rows.size());
-      if ((e = up(d[0], rows)) != hipSuccess || (e = up(d[1], ptr)) != hipSuccess || (e = up(d[2], src)) != hipSuccess) return e;
-      gx_long = build_rhs_csr(h->h_vindex, rows, ptr, src);
-      n_gx = int(rows.size());
-      if ((e = up(d[3], rows)) != hipSuccess || (e = up(d[4], ptr)) != hipSuccess || (e = up(d[5], src)) != hipSuccess) return e;
-      if ((e = hipMalloc(&fxb, sizeof(double) * size_t(h->nseg) * OR)) != hipSuccess) return e;
-      return hipMalloc(&agxb, sizeof(double) * size_t(h->nseg) * IR);
-    };
-    const hipError_t e = build();
-    if (e != hipSuccess) {   // nothing of a half-built set stays on the handle: the next call starts over
-      for (int* p : d) if (p) hipFree(p);
-      if (fxb) hipFree(fxb);
-      if (agxb) hipFree(agxb);
-      return hipfail(e, "building the RHS gather tables");
-    }
-    h->d_fx_rows = d[0], h->d_fx_ptr = d[1], h->d_fx_src = d[2], h->d_gx_rows = d[3], h->d_gx_ptr = d[4], h->d_gx_src = d[5];
-    h->d_fxb = fxb, h->d_agxb = agxb;
-    h->n_fx_rows = n_fx, h->fx_long_from = fx_long, h->n_gx_rows = n_gx, h->gx_long_from = gx_long;
-    h->rhs_tables_ready = true;
+  hipStream_t st = stream_or(h, stream);
+  if (!h->rhs.agxb) {   // the gather tables, once per mesh: built into a local, committed only when all of them exist
+    asset_hip_defect::RhsTables fresh;
+    HIP_TRY_AS(build_rhs_tables(h, fresh), "building the RHS gather tables");
+    h->rhs = std::move(fresh);
   }
-  int rc = launch(h, what, dX, dL, h->d_fxb, want_agx ? h->d_agxb : nullptr, nullptr, st, want_kkt ? d_kkt_values : nullptr);
+  const asset_hip_defect::RhsTables& r = h->rhs;
+  int rc = launch(h, what, dX, dL, r.fxb.get(), want_agx ? r.agxb.get() : nullptr, nullptr, st, want_kkt ? d_kkt_values : nullptr);
   if (rc) return rc;
   auto gather = [&](double* target, const double* blocks, const int* rows, const int* ptr, const int* src, int nrows,
                     int long_from) -> hipError_t {
@@ -1264,8 +1130,8 @@ int asset_hip_defect_eval_kkt_device(asset_hip_defect_t h, int what, const doubl
                          ptr, src, long_from);
     return hipGetLastError();
   };
-  HIP_TRY(gather(d_FXE, h->d_fxb, h->d_fx_rows, h->d_fx_ptr, h->d_fx_src, h->n_fx_rows, h->fx_long_from));
-  if (want_agx) HIP_TRY(gather(d_AGX, h->d_agxb, h->d_gx_rows, h->d_gx_ptr, h->d_gx_src, h->n_gx_rows, h->gx_long_from));
+  HIP_TRY(gather(d_FXE, r.fxb.get(), r.fx_rows.get(), r.fx_ptr.get(), r.fx_src.get(), r.n_fx_rows, r.fx_long_from));
+  if (want_agx) HIP_TRY(gather(d_AGX, r.agxb.get(), r.gx_rows.get(), r.gx_ptr.get(), r.gx_src.get(), r.n_gx_rows, r.gx_long_from));
   return 0;
 }
 
@@ -1287,44 +1153,41 @@ static int eval_assembled_host(asset_hip_defect_t h, int what, const double* X, 
   if (!h) return fail(ASSET_HIP_EINVAL, "null handle");
   if (!X || !kkt_values) return fail(ASSET_HIP_EINVAL, "X / kkt value array is null");
   if (what < ASSET_HIP_JAC) return fail(ASSET_HIP_EINVAL, "assembled evaluation needs a kind that produces KKT entries");
-  if (!h->d_map) return fail(ASSET_HIP_EINVAL, "no kkt map: call asset_hip_defect_set_kkt_map first");
+  if (!h->kmap.map) return fail(ASSET_HIP_EINVAL, "no kkt map: call asset_hip_defect_set_kkt_map first");
   HIP_TRY(hipSetDevice(h->device));
+  asset_hip_defect::DeviceKktMap& k = h->kmap;
   const size_t nfx = size_t(h->nseg) * h->ke->orr, nagx = size_t(h->nseg) * h->ke->ir;
-  const size_t nval = size_t(h->value_hi - h->value_lo);
-  if (!h->d_X) HIP_TRY(hipMalloc(&h->d_X, sizeof(double) * h->cap_primal));
-  if (!h->d_L) HIP_TRY(hipMalloc(&h->d_L, sizeof(double) * h->cap_equal));
-  if (fx_blocks && !h->d_fx) HIP_TRY(hipMalloc(&h->d_fx, sizeof(double) * size_t(h->cap_seg) * h->ke->orr));
-  if (agx_blocks && !h->d_agx) HIP_TRY(hipMalloc(&h->d_agx, sizeof(double) * size_t(h->cap_seg) * h->ke->ir));
-  if (!h->d_values) {
-    HIP_TRY(hipMalloc(&h->d_values, sizeof(double) * nval));
-    HIP_TRY(hipHostMalloc(&h->h_values, sizeof(double) * nval, hipHostMallocDefault));
+  const size_t nval = size_t(k.value_hi - k.value_lo);
+  if (!k.h_values) {   // (the pinned mirror is the second of the pair: a call that got only the first starts over)
+    HIP_TRY(k.d_values.allocate(nval));
+    HIP_TRY(k.h_values.allocate(nval));
   }
-  HIP_TRY(hipMemcpyAsync(h->d_X, X, sizeof(double) * h->n_primal, hipMemcpyHostToDevice, h->stream));
-  if (L) HIP_TRY(hipMemcpyAsync(h->d_L, L, sizeof(double) * h->n_equal, hipMemcpyHostToDevice, h->stream));
-  HIP_TRY(hipMemsetAsync(h->d_values, 0, sizeof(double) * nval, h->stream));
+  int rc = stage_inputs(h, X, L, fx_blocks, agx_blocks, false);
+  if (rc) return rc;
+  const asset_hip_defect::HostStaging& s = h->staging;
+  hipStream_t st = h->stream.get();
+  HIP_TRY(hipMemsetAsync(k.d_values.get(), 0, sizeof(double) * nval, st));
   // The device array covers [value_lo, value_hi) of the caller's: bias the base address so that locations index it
   // directly (integer arithmetic: the biased address is only ever used with offsets >= value_lo).
-  double* biased = reinterpret_cast<double*>(reinterpret_cast<uintptr_t>(h->d_values) -
-                                             uintptr_t(h->value_lo) * sizeof(double));
-  int rc = asset_hip_defect_eval_assembled_device(h, what, h->d_X, L ? h->d_L : nullptr, fx_blocks ? h->d_fx : nullptr,
-                                                  agx_blocks ? h->d_agx : nullptr, biased, h->stream);
+  double* biased = reinterpret_cast<double*>(reinterpret_cast<uintptr_t>(k.d_values.get()) - uintptr_t(k.value_lo) * sizeof(double));
+  rc = asset_hip_defect_eval_assembled_device(h, what, s.X.get(), L ? s.L.get() : nullptr, fx_blocks ? s.fx.get() : nullptr,
+                                              agx_blocks ? s.agx.get() : nullptr, biased, st);
   if (rc) return rc;
-  if (fx_blocks) HIP_TRY(hipMemcpyAsync(fx_blocks, h->d_fx, sizeof(double) * nfx, hipMemcpyDeviceToHost, h->stream));
-  if (agx_blocks && what != ASSET_HIP_JAC)
-    HIP_TRY(hipMemcpyAsync(agx_blocks, h->d_agx, sizeof(double) * nagx, hipMemcpyDeviceToHost, h->stream));
+  if (fx_blocks) HIP_TRY(hipMemcpyAsync(fx_blocks, s.fx.get(), sizeof(double) * nfx, hipMemcpyDeviceToHost, st));
+  if (agx_blocks && what != ASSET_HIP_JAC) HIP_TRY(hipMemcpyAsync(agx_blocks, s.agx.get(), sizeof(double) * nagx, hipMemcpyDeviceToHost, st));
   if (target_zeroed) {
     // the caller's range holds zeros (it was just cleared and this constraint is the first to fill it): the values go
     // straight into it -- by DMA when the array is page-locked (asset_hip_host_register), through the driver's staging
     // otherwise -- and no host pass over the values is needed at all
-    HIP_TRY(hipMemcpyAsync(kkt_values + h->value_lo, h->d_values, sizeof(double) * nval, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
+    HIP_TRY(hipMemcpyAsync(kkt_values + k.value_lo, k.d_values.get(), sizeof(double) * nval, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
     return 0;
   }
-  HIP_TRY(hipMemcpyAsync(h->h_values, h->d_values, sizeof(double) * nval, hipMemcpyDeviceToHost, h->stream));
-  HIP_TRY(hipStreamSynchronize(h->stream));
+  HIP_TRY(hipMemcpyAsync(k.h_values.get(), k.d_values.get(), sizeof(double) * nval, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
   // accumulate, as the reference's fill does: O(nnz) contiguous adds, split over a few threads (memory-bound)
-  double* dst = kkt_values + h->value_lo;
-  const double* src = h->h_values;
+  double* dst = kkt_values + k.value_lo;
+  const double* src = k.h_values.get();
   const unsigned hw = std::thread::hardware_concurrency();
   const size_t nthr = nval < (size_t(1) << 18) ? 1 : (hw >= 8 ? 8 : (hw ? hw : 1));
   auto add = [=](size_t b, size_t e) { for (size_t i = b; i < e; i++) dst[i] += src[i]; };

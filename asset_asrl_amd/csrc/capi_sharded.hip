@@ -11,25 +11,41 @@
 #include <algorithm>
 #include <cstdint>
 #include <cstring>
+#include <memory>
 #include <new>
 #include <string>
 #include <thread>
 #include <vector>
 
 #include "../../include/asset_hip.h"
-
-extern "C" __attribute__((visibility("hidden"))) void asset_hip_set_last_error(const char* msg);   // capi.hip
+#include "capi/owners.h"
 
 namespace {
-struct Shard {
-  int device = 0, first = 0, count = 0;
-  asset_hip_defect_t h = nullptr;
-  hipStream_t stream = nullptr;
-  double *dX = nullptr, *dL = nullptr, *dfx = nullptr, *dagx = nullptr, *dkkt = nullptr;
-  // assembled form: this shard's range [lo, hi) of the solver's value array, on the device and in page-locked host memory
+using asset_hip::DeviceBuffer;
+using asset_hip::DeviceGuard;
+using asset_hip::wants_kkt;
+using asset_hip::wants_multipliers;
+
+// assembled form: a shard's range [lo, hi) of the solver's value array, on its device and in page-locked host memory
+struct ShardValues {
+  int device = 0;
   long long lo = 0, hi = 0;
-  double* dvals = nullptr;
-  double* hvals = nullptr;
+  DeviceBuffer<double> d;
+  asset_hip::PinnedBuffer<double> h;
+  ShardValues() = default;
+  ShardValues(ShardValues&&) = default;
+  ShardValues& operator=(ShardValues&&) = default;
+  ~ShardValues() { if (d || h) (void)hipSetDevice(device); }   // (the buffers go after this body, on their device)
+};
+struct DefectDestroy {
+  void operator()(asset_hip_defect_t h) const { asset_hip_defect_destroy(h); }
+};
+struct Shard {   // (what goes last comes first: the buffers, then the stream, then the handle)
+  int device = 0, first = 0, count = 0;
+  std::unique_ptr<asset_hip_defect, DefectDestroy> h;
+  asset_hip::Stream stream;
+  DeviceBuffer<double> dX, dL, dfx, dagx, dkkt;
+  ShardValues vals;
 };
 int sfail(int rc, const std::string& msg) {
   asset_hip_set_last_error(msg.c_str());
@@ -38,14 +54,12 @@ int sfail(int rc, const std::string& msg) {
 int hfail(hipError_t e, const char* where) {
   return sfail(int(e), std::string(where) + ": " + hipGetErrorString(e));
 }
-// Every entry point below walks the shards' devices (hipSetDevice is per thread): the calling thread's current device is put back on
-// every exit path, so that a caller who also uses torch or another HIP client on this thread does not find its later allocations and
-// launches on the last shard's GPU.
-struct DeviceGuard {
-  int dev = -1;
-  DeviceGuard() { if (hipGetDevice(&dev) != hipSuccess) { dev = -1; (void)hipGetLastError(); } }
-  ~DeviceGuard() { if (dev >= 0) (void)hipSetDevice(dev); }
-};
+#define HIP_TRY_AS(expr, where)                        \
+  do {                                                 \
+    hipError_t _e = (expr);                            \
+    if (_e != hipSuccess) return hfail(_e, where);     \
+  } while (0)
+// (every entry point below walks the shards' devices under a DeviceGuard: capi/owners.h)
 // Is the range a device-to-host copy may land in page-locked (hipHostMalloc / asset_hip_host_register)?  Into pageable memory
 // hipMemcpyAsync is synchronous for the calling thread.
 bool page_locked(const void* p) {
@@ -69,13 +83,9 @@ void asset_hip_sharded_destroy(asset_hip_sharded_t s) {
   if (!s) return;
   DeviceGuard guard;
   for (Shard& sh : s->shards) {
-    if (sh.stream || sh.dX) (void)hipSetDevice(sh.device);
-    if (sh.stream) (void)hipStreamSynchronize(sh.stream);
-    for (double* p : {sh.dX, sh.dL, sh.dfx, sh.dagx, sh.dkkt, sh.dvals})
-      if (p) (void)hipFree(p);
-    if (sh.hvals) (void)hipHostFree(sh.hvals);
-    if (sh.stream) (void)hipStreamDestroy(sh.stream);
-    if (sh.h) asset_hip_defect_destroy(sh.h);
+    if (sh.stream.get() || sh.dX) (void)hipSetDevice(sh.device);
+    if (sh.stream.get()) (void)hipStreamSynchronize(sh.stream.get());
+    { Shard gone(std::move(sh)); }   // on its device
   }
   delete s;
 }
@@ -84,56 +94,49 @@ int asset_hip_defect_create_sharded(const asset_hip_defect_desc* d, int nshards,
   if (!d || !out || !devices || nshards <= 0) return sfail(ASSET_HIP_EINVAL, "create_sharded: null descriptor / devices / output, or no shards");
   *out = nullptr;
   if (!d->vindex || !d->cindex || d->nseg <= 0) return sfail(ASSET_HIP_EINVAL, "create_sharded: descriptor fields missing or non-positive");
-  {
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
-      (void)hipGetLastError();
-      return sfail(ASSET_HIP_ENODEV, "no HIP device visible: the evaluator has no CPU fallback");
-    }
-    for (int i = 0; i < nshards; i++)
-      if (devices[i] < 0 || devices[i] >= ndev) return sfail(ASSET_HIP_EINVAL, "create_sharded: device ordinal out of range");
-  }
   DeviceGuard guard;
-  asset_hip_sharded* s = new (std::nothrow) asset_hip_sharded;
+  for (int i = 0; i < nshards; i++)
+    if (const int rc = asset_hip::use_device(devices[i], "no HIP device visible: the evaluator has no CPU fallback")) return rc;
+  // (a failing path below returns: what exists by then goes as asset_hip_sharded_destroy lets it go)
+  std::unique_ptr<asset_hip_sharded, void (*)(asset_hip_sharded_t)> s(new (std::nothrow) asset_hip_sharded, asset_hip_sharded_destroy);
   if (!s) return sfail(ASSET_HIP_EINVAL, "out of host memory");
   s->nseg = d->nseg, s->n_primal = d->n_primal, s->n_equal = d->n_equal;
   // IndexingData.h:117-146: cols / Threads each, the first cols % Threads one more; fewer shards than asked for when there are
   // fewer applications than shards
   const int per = d->nseg / nshards, rem = d->nseg % nshards, range = per > 0 ? nshards : rem;
+  s->shards.resize(range);
   int start = 0;
   for (int i = 0; i < range; i++) {
-    Shard sh;
-    sh.device = devices[i], sh.first = start, sh.count = per + (i < rem ? 1 : 0);
+    Shard& sh = s->shards[i];
+    sh.device = sh.vals.device = devices[i], sh.first = start, sh.count = per + (i < rem ? 1 : 0);
     start += sh.count;
-    s->shards.push_back(sh);
   }
   for (size_t i = 0; i < s->shards.size(); i++) {
     Shard& sh = s->shards[i];
     asset_hip_defect_desc sd = *d;
     sd.device = sh.device;
     sd.nseg = sh.count;
-    int rc = 0;
-    if (i == 0) {                                       // sizes from the first handle (the tables of the others start IR / OR rows further on)
-      rc = asset_hip_defect_create(&sd, &sh.h);
-      if (rc == 0) rc = asset_hip_defect_sizes(sh.h, &s->ir, &s->orr, &s->nkkt);
-      if (rc == 0 && asset_hip_defect_kkt_layout(sh.h, &s->kstride, nullptr, nullptr) < 0) rc = ASSET_HIP_EINVAL;
-    } else {
+    if (i > 0) {                                        // (the tables of the others start IR / OR rows further on)
       sd.vindex = d->vindex + size_t(sh.first) * s->ir;
       sd.cindex = d->cindex + size_t(sh.first) * s->orr;
-      rc = asset_hip_defect_create(&sd, &sh.h);
     }
-    if (rc) { asset_hip_sharded_destroy(s); return rc; }
-    hipError_t e;
-    auto bail = [&](hipError_t err, const char* w) { int r = hfail(err, w); asset_hip_sharded_destroy(s); return r; };
-    if ((e = hipSetDevice(sh.device)) != hipSuccess) return bail(e, "hipSetDevice");
-    if ((e = hipStreamCreateWithFlags(&sh.stream, hipStreamNonBlocking)) != hipSuccess) return bail(e, "hipStreamCreate");
-    if ((e = hipMalloc(&sh.dX, size_t(d->n_primal) * 8)) != hipSuccess) return bail(e, "hipMalloc(X)");
-    if ((e = hipMalloc(&sh.dL, size_t(d->n_equal) * 8)) != hipSuccess) return bail(e, "hipMalloc(L)");
-    if ((e = hipMalloc(&sh.dfx, size_t(sh.count) * s->orr * 8)) != hipSuccess) return bail(e, "hipMalloc(FX blocks)");
-    if ((e = hipMalloc(&sh.dagx, size_t(sh.count) * s->ir * 8)) != hipSuccess) return bail(e, "hipMalloc(AGX blocks)");
-    if ((e = hipMalloc(&sh.dkkt, size_t(sh.count) * s->kstride * 8)) != hipSuccess) return bail(e, "hipMalloc(KKT blocks)");
+    asset_hip_defect_t h = nullptr;
+    int rc = asset_hip_defect_create(&sd, &h);
+    sh.h.reset(h);
+    if (rc == 0 && i == 0) {                            // sizes from the first handle
+      rc = asset_hip_defect_sizes(h, &s->ir, &s->orr, &s->nkkt);
+      if (rc == 0 && asset_hip_defect_kkt_layout(h, &s->kstride, nullptr, nullptr) < 0) rc = ASSET_HIP_EINVAL;
+    }
+    if (rc) return rc;
+    HIP_TRY_AS(hipSetDevice(sh.device), "hipSetDevice");
+    HIP_TRY_AS(sh.stream.create(), "hipStreamCreate");
+    HIP_TRY_AS(sh.dX.allocate(size_t(d->n_primal)), "hipMalloc(X)");
+    HIP_TRY_AS(sh.dL.allocate(size_t(d->n_equal)), "hipMalloc(L)");
+    HIP_TRY_AS(sh.dfx.allocate(size_t(sh.count) * s->orr), "hipMalloc(FX blocks)");
+    HIP_TRY_AS(sh.dagx.allocate(size_t(sh.count) * s->ir), "hipMalloc(AGX blocks)");
+    HIP_TRY_AS(sh.dkkt.allocate(size_t(sh.count) * s->kstride), "hipMalloc(KKT blocks)");
   }
-  *out = s;
+  *out = s.release();
   return 0;
 }
 
@@ -148,7 +151,7 @@ int asset_hip_sharded_range(asset_hip_sharded_t s, int shard, int* first, int* c
 }
 
 asset_hip_defect_t asset_hip_sharded_handle(asset_hip_sharded_t s, int shard) {
-  return (s && shard >= 0 && shard < int(s->shards.size())) ? s->shards[shard].h : nullptr;
+  return (s && shard >= 0 && shard < int(s->shards.size())) ? s->shards[shard].h.get() : nullptr;
 }
 
 }  // extern "C"
@@ -157,15 +160,15 @@ asset_hip_defect_t asset_hip_sharded_handle(asset_hip_sharded_t s, int shard) {
 static int upload(asset_hip_sharded_t s, Shard& sh, const double* X, const double* L) {
   hipError_t e;
   if ((e = hipSetDevice(sh.device)) != hipSuccess) return hfail(e, "hipSetDevice");
-  if ((e = hipMemcpyAsync(sh.dX, X, size_t(s->n_primal) * 8, hipMemcpyHostToDevice, sh.stream)) != hipSuccess) return hfail(e, "hipMemcpyAsync(X)");
-  if (L && (e = hipMemcpyAsync(sh.dL, L, size_t(s->n_equal) * 8, hipMemcpyHostToDevice, sh.stream)) != hipSuccess) return hfail(e, "hipMemcpyAsync(L)");
+  if ((e = hipMemcpyAsync(sh.dX.get(), X, size_t(s->n_primal) * 8, hipMemcpyHostToDevice, sh.stream.get())) != hipSuccess) return hfail(e, "hipMemcpyAsync(X)");
+  if (L && (e = hipMemcpyAsync(sh.dL.get(), L, size_t(s->n_equal) * 8, hipMemcpyHostToDevice, sh.stream.get())) != hipSuccess) return hfail(e, "hipMemcpyAsync(L)");
   return 0;
 }
 static int drain(asset_hip_sharded_t s) {
   int rc = 0;
   for (Shard& sh : s->shards) {
     hipError_t e = hipSetDevice(sh.device);
-    if (e == hipSuccess) e = hipStreamSynchronize(sh.stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(sh.stream.get());
     if (e != hipSuccess && rc == 0) rc = hfail(e, "hipStreamSynchronize(shard)");
   }
   return rc;
@@ -177,16 +180,17 @@ static int shard_eval(asset_hip_sharded_t s, Shard& sh, int what, const double* 
                       double* kkt_blocks, bool want_agx, bool want_kkt, bool wait) {
   int rc = upload(s, sh, X, L);
   if (rc) return rc;
-  rc = asset_hip_defect_eval_device(sh.h, what, sh.dX, L ? sh.dL : nullptr, fx_blocks ? sh.dfx : nullptr, want_agx ? sh.dagx : nullptr,
-                                    want_kkt ? sh.dkkt : nullptr, sh.stream);
+  hipStream_t st = sh.stream.get();
+  rc = asset_hip_defect_eval_device(sh.h.get(), what, sh.dX.get(), L ? sh.dL.get() : nullptr, fx_blocks ? sh.dfx.get() : nullptr,
+                                    want_agx ? sh.dagx.get() : nullptr, want_kkt ? sh.dkkt.get() : nullptr, st);
   if (rc) return rc;
   hipError_t e = hipSuccess;
-  if (fx_blocks) e = hipMemcpyAsync(fx_blocks + size_t(sh.first) * s->orr, sh.dfx, size_t(sh.count) * s->orr * 8, hipMemcpyDeviceToHost, sh.stream);
+  if (fx_blocks) e = hipMemcpyAsync(fx_blocks + size_t(sh.first) * s->orr, sh.dfx.get(), size_t(sh.count) * s->orr * 8, hipMemcpyDeviceToHost, st);
   if (e == hipSuccess && want_agx)
-    e = hipMemcpyAsync(agx_blocks + size_t(sh.first) * s->ir, sh.dagx, size_t(sh.count) * s->ir * 8, hipMemcpyDeviceToHost, sh.stream);
+    e = hipMemcpyAsync(agx_blocks + size_t(sh.first) * s->ir, sh.dagx.get(), size_t(sh.count) * s->ir * 8, hipMemcpyDeviceToHost, st);
   if (e == hipSuccess && want_kkt)
-    e = hipMemcpyAsync(kkt_blocks + size_t(sh.first) * s->kstride, sh.dkkt, size_t(sh.count) * s->kstride * 8, hipMemcpyDeviceToHost, sh.stream);
-  if (e == hipSuccess && wait) e = hipStreamSynchronize(sh.stream);
+    e = hipMemcpyAsync(kkt_blocks + size_t(sh.first) * s->kstride, sh.dkkt.get(), size_t(sh.count) * s->kstride * 8, hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess && wait) e = hipStreamSynchronize(st);
   return e == hipSuccess ? 0 : hfail(e, "hipMemcpyAsync(blocks)");
 }
 
@@ -223,9 +227,8 @@ int asset_hip_sharded_eval(asset_hip_sharded_t s, int what, const double* X, con
                            double* kkt_blocks) {
   if (!s || !X) return sfail(ASSET_HIP_EINVAL, "sharded_eval: null handle / X");
   DeviceGuard guard;
-  const int kind = what & 0xff;
-  const bool want_agx = agx_blocks && (kind == ASSET_HIP_CON_ADJGRAD || kind == ASSET_HIP_JAC_ADJGRAD || kind == ASSET_HIP_JAC_ADJGRAD_HESS);
-  const bool want_kkt = kkt_blocks && kind >= ASSET_HIP_JAC;
+  const bool want_agx = agx_blocks && wants_multipliers(what);
+  const bool want_kkt = kkt_blocks && wants_kkt(what);
   // every shard enqueued before any is waited for (NonLinearProgram.cpp:519-526) -- which a single enqueueing thread can only do
   // when no copy blocks it
   // (X / L: a pageable source costs the issuing thread the staging of 8 (n_primal + n_equal) bytes per shard, ahead of the shard's
@@ -245,16 +248,7 @@ int asset_hip_sharded_set_kkt_map(asset_hip_sharded_t s, const int32_t* slot_loc
   // EVERY shard has its new map and its new buffers; the buffers are built into locals and committed together.
   s->nvalues = 0;
   const size_t n = s->shards.size();
-  struct Fresh { long long lo = 0, hi = 0; double* d = nullptr; double* h = nullptr; };
-  std::vector<Fresh> fresh(n);
-  auto undo = [&](int rc) {
-    for (size_t i = 0; i < n; i++) {
-      if (fresh[i].d || fresh[i].h) (void)hipSetDevice(s->shards[i].device);
-      if (fresh[i].d) (void)hipFree(fresh[i].d);
-      if (fresh[i].h) (void)hipHostFree(fresh[i].h);
-    }
-    return rc;
-  };
+  std::vector<ShardValues> fresh(n);
   std::vector<int32_t> local;
   for (size_t i = 0; i < n; i++) {
     Shard& sh = s->shards[i];
@@ -264,24 +258,20 @@ int asset_hip_sharded_set_kkt_map(asset_hip_sharded_t s, const int32_t* slot_loc
     for (size_t k = 0; k < len; k++)
       if (m[k] >= 0) { lo = std::min<long long>(lo, m[k]); hi = std::max<long long>(hi, (long long)m[k] + 1); }
     if (hi <= lo) lo = 0, hi = 1;
-    if (hi > nvalues) return undo(sfail(ASSET_HIP_ERANGE, "sharded_set_kkt_map: a slot location is outside the value array"));
+    if (hi > nvalues) return sfail(ASSET_HIP_ERANGE, "sharded_set_kkt_map: a slot location is outside the value array");
     local.resize(len);
     for (size_t k = 0; k < len; k++) local[k] = m[k] >= 0 ? int32_t(m[k] - lo) : -1;   // the shard's own array starts at its lowest location
-    const int rc = asset_hip_defect_set_kkt_map(sh.h, local.data(), hi - lo, 0);
-    if (rc) return undo(rc);
-    hipError_t e;
-    if ((e = hipSetDevice(sh.device)) != hipSuccess) return undo(hfail(e, "hipSetDevice"));
-    if ((e = hipMalloc(&fresh[i].d, size_t(hi - lo) * 8)) != hipSuccess) return undo(hfail(e, "hipMalloc(shard values)"));
-    if ((e = hipHostMalloc(reinterpret_cast<void**>(&fresh[i].h), size_t(hi - lo) * 8, hipHostMallocDefault)) != hipSuccess)
-      return undo(hfail(e, "hipHostMalloc(shard values)"));
-    fresh[i].lo = lo, fresh[i].hi = hi;
+    const int rc = asset_hip_defect_set_kkt_map(sh.h.get(), local.data(), hi - lo, 0);
+    if (rc) return rc;
+    fresh[i].device = sh.device, fresh[i].lo = lo, fresh[i].hi = hi;
+    HIP_TRY_AS(hipSetDevice(sh.device), "hipSetDevice");
+    HIP_TRY_AS(fresh[i].d.allocate(size_t(hi - lo)), "hipMalloc(shard values)");
+    HIP_TRY_AS(fresh[i].h.allocate(size_t(hi - lo)), "hipHostMalloc(shard values)");
   }
   for (size_t i = 0; i < n; i++) {
     Shard& sh = s->shards[i];
-    if (sh.dvals || sh.hvals) (void)hipSetDevice(sh.device);
-    if (sh.dvals) (void)hipFree(sh.dvals);
-    if (sh.hvals) (void)hipHostFree(sh.hvals);
-    sh.dvals = fresh[i].d, sh.hvals = fresh[i].h, sh.lo = fresh[i].lo, sh.hi = fresh[i].hi;
+    if (sh.vals.d || sh.vals.h) (void)hipSetDevice(sh.device);
+    sh.vals = std::move(fresh[i]);
   }
   s->nvalues = nvalues;
   return 0;
@@ -291,26 +281,27 @@ int asset_hip_sharded_eval_assembled(asset_hip_sharded_t s, int what, const doub
                                      double* agx_blocks, double* kkt_values) {
   if (!s || !X || !kkt_values) return sfail(ASSET_HIP_EINVAL, "sharded_eval_assembled: null handle / X / values");
   if (s->nvalues <= 0) return sfail(ASSET_HIP_EINVAL, "sharded_eval_assembled: no KKT map (asset_hip_sharded_set_kkt_map)");
-  const int kind = what & 0xff;
-  if (kind < ASSET_HIP_JAC) return sfail(ASSET_HIP_EINVAL, "sharded_eval_assembled: a Jacobian kind is expected");
+  if (!wants_kkt(what)) return sfail(ASSET_HIP_EINVAL, "sharded_eval_assembled: a Jacobian kind is expected");
   DeviceGuard guard;
-  const bool want_agx = agx_blocks && (kind == ASSET_HIP_JAC_ADJGRAD || kind == ASSET_HIP_JAC_ADJGRAD_HESS);
+  const bool want_agx = agx_blocks && wants_multipliers(what);
   // (the values always land in the shards' own page-locked staging; the FX / AGX blocks in the caller's arrays)
   const bool async = page_locked(fx_blocks) && (!want_agx || page_locked(agx_blocks));
   const int rc = for_shards(s, async, [&](Shard& sh) {
     int r = upload(s, sh, X, L);
     if (r) return r;
-    hipError_t e = hipMemsetAsync(sh.dvals, 0, size_t(sh.hi - sh.lo) * 8, sh.stream);
+    hipStream_t st = sh.stream.get();
+    const size_t nval = size_t(sh.vals.hi - sh.vals.lo);
+    hipError_t e = hipMemsetAsync(sh.vals.d.get(), 0, nval * 8, st);
     if (e != hipSuccess) return hfail(e, "hipMemsetAsync(shard values)");
-    r = asset_hip_defect_eval_assembled_device(sh.h, what, sh.dX, L ? sh.dL : nullptr, fx_blocks ? sh.dfx : nullptr,
-                                               want_agx ? sh.dagx : nullptr, sh.dvals, sh.stream);
+    r = asset_hip_defect_eval_assembled_device(sh.h.get(), what, sh.dX.get(), L ? sh.dL.get() : nullptr, fx_blocks ? sh.dfx.get() : nullptr,
+                                               want_agx ? sh.dagx.get() : nullptr, sh.vals.d.get(), st);
     if (r) return r;
-    e = hipMemcpyAsync(sh.hvals, sh.dvals, size_t(sh.hi - sh.lo) * 8, hipMemcpyDeviceToHost, sh.stream);
+    e = hipMemcpyAsync(sh.vals.h.get(), sh.vals.d.get(), nval * 8, hipMemcpyDeviceToHost, st);
     if (e == hipSuccess && fx_blocks)
-      e = hipMemcpyAsync(fx_blocks + size_t(sh.first) * s->orr, sh.dfx, size_t(sh.count) * s->orr * 8, hipMemcpyDeviceToHost, sh.stream);
+      e = hipMemcpyAsync(fx_blocks + size_t(sh.first) * s->orr, sh.dfx.get(), size_t(sh.count) * s->orr * 8, hipMemcpyDeviceToHost, st);
     if (e == hipSuccess && want_agx)
-      e = hipMemcpyAsync(agx_blocks + size_t(sh.first) * s->ir, sh.dagx, size_t(sh.count) * s->ir * 8, hipMemcpyDeviceToHost, sh.stream);
-    if (e == hipSuccess && !async) e = hipStreamSynchronize(sh.stream);
+      e = hipMemcpyAsync(agx_blocks + size_t(sh.first) * s->ir, sh.dagx.get(), size_t(sh.count) * s->ir * 8, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess && !async) e = hipStreamSynchronize(st);
     return e == hipSuccess ? 0 : hfail(e, "hipMemcpyAsync(shard values / blocks)");
   });
   const int rd = drain(s);
@@ -322,15 +313,15 @@ int asset_hip_sharded_eval_assembled(asset_hip_sharded_t s, int what, const doub
   // every shard's overlap with its piece in shard order -- no two threads write one location, and every location sees its
   // contributions in the order of the serial loop.
   long long lo = s->nvalues, hi = 0;
-  for (Shard& sh : s->shards) lo = std::min(lo, sh.lo), hi = std::max(hi, sh.hi);
+  for (Shard& sh : s->shards) lo = std::min(lo, sh.vals.lo), hi = std::max(hi, sh.vals.hi);
   const long long total = hi > lo ? hi - lo : 0;
   unsigned hw = std::thread::hardware_concurrency();
   const int nt = int(std::max<long long>(1, std::min<long long>({(long long)(hw ? hw : 1), 16LL, total / (1 << 18)})));   // (>= 2 MiB of values per thread)
   auto add_piece = [&](long long a, long long b) {
     for (Shard& sh : s->shards) {
-      const long long x = std::max(a, sh.lo), y = std::min(b, sh.hi);
+      const long long x = std::max(a, sh.vals.lo), y = std::min(b, sh.vals.hi);
       double* dst = kkt_values + x;
-      const double* src = sh.hvals + (x - sh.lo);
+      const double* src = sh.vals.h.get() + (x - sh.vals.lo);
       for (long long k = 0; k < y - x; k++) dst[k] += src[k];
     }
   };

@@ -246,6 +246,16 @@ int asset_hip_host_unregister(void* ptr);
  * asset_hip_defect_eval_assembled_device: everything resident in HBM; d_kkt_values[nvalues] receives the entries
  * as the map's mode prescribes, on `stream`, not synchronised. */
 int asset_hip_defect_set_kkt_map(asset_hip_defect_t h, const int32_t* slot_locations, long long nvalues, int accumulate);
+/* What asset_hip_defect_set_kkt_map builds from the same arguments, without a handle and without a device: ir / orr are the
+ * function's input and output rows (asset_hip_defect_sizes), plain_function != 0 for ASSET_HIP_FUNCTION handles (entries placed
+ * slot by slot instead of in the accumulator-fragment order of the transcriptions).  Every output may be NULL; a first call with
+ * NULL arrays gives the lengths: map_words[*map_len], multi_loc[*nmulti], multi_ptr[*nmulti + 1].  A map word m >= 0 stores to
+ * location m, -1 drops the entry, -(m + 2) with m < nvalues adds atomically to location m, and -(nvalues + c + 2) writes staging
+ * cell c; the cells multi_ptr[l] .. multi_ptr[l + 1] are summed in order into location multi_loc[l].  [*lo, *hi) is the range of
+ * the value array the map touches.  Same error codes and texts as asset_hip_defect_set_kkt_map. */
+int asset_hip_kkt_map_query(int ir, int orr, int plain_function, int nseg, const int32_t* slot_locations, long long nvalues,
+                            int accumulate, long long* map_len, int32_t* map_words, int* nmulti, int32_t* multi_ptr,
+                            int32_t* multi_loc, long long* lo, long long* hi);
 int asset_hip_defect_eval_assembled(asset_hip_defect_t h, int what, const double* X, const double* L, double* fx_blocks,
                                     double* agx_blocks, double* kkt_values);
 int asset_hip_defect_eval_assembled_device(asset_hip_defect_t h, int what, const double* dX, const double* dL,
