@@ -398,6 +398,15 @@ int asset_hip_has_kernel(const char* ode, int mode, int blocked) {
 
 int asset_hip_lgl_table(int cs, const char* which, double* out, int cap) {
   if (cs < 2 || cs > 4 || !which || !out) return fail(ASSET_HIP_EINVAL, "bad lgl table query");
+  const bool trap = !std::strcmp(which, "mesh_trapezoidal");
+  if (trap || !std::strcmp(which, "mesh")) {   // the estimator's scheme (mesh_kernels.h): order, error weight, factorial, xw[cs], dxw[cs]
+    if (trap && cs != 2) return fail(ASSET_HIP_EINVAL, "the Trapezoidal scheme has two nodes");
+    const asset_hip::MeshScheme sc = asset_hip::mesh_scheme(trap ? 1 : cs);   // (LGL modes carry their cs as the mode number)
+    if (cap < 3 + 2 * cs) return fail(ASSET_HIP_EINVAL, "output buffer too small");
+    out[0] = sc.order, out[1] = sc.error_weight, out[2] = sc.factorial;
+    for (int j = 0; j < cs; j++) out[3 + j] = sc.xw[j], out[3 + cs + j] = sc.dxw[j];
+    return 3 + 2 * cs;
+  }
   const asset_hip::LglTab& t = asset_hip::h_lgl_tab[cs - 2];
   const int K = cs - 1;
   const double* src = nullptr;

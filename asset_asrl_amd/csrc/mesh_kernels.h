@@ -42,7 +42,7 @@ struct MeshArgs {
   double* tsnd;         // [nb+1]
   double* errors;       // [nb+1][n]  (= xv x (nb+1) column-major, the reference's Eigen layout)
   double* dist;         // [nb+1][n]
-  double* error_max;    // [nb+1] infinity norm over the states
+  double* error_max;    // [nb+1] infinity norm over the states; NaN when a state's entry is NaN
   double* dist_max;     // [nb+1]
 };
 
@@ -114,8 +114,9 @@ __global__ __launch_bounds__(64) void mesh_error_kernel(MeshArgs a, int n, doubl
     const double dv = pow(e, ipow), ev = e * scale;
     a.dist[size_t(i) * n + k] = dv;
     a.errors[size_t(i) * n + k] = ev;
-    emax = fmax(emax, fabs(ev));
-    dmax = fmax(dmax, fabs(dv));
+    // a NaN entry makes the block's maximum NaN (numpy's maximum; fmax would drop it), and a NaN maximum stays
+    emax = (fabs(ev) > emax || ev != ev) ? fabs(ev) : emax;
+    dmax = (fabs(dv) > dmax || dv != dv) ? fabs(dv) : dmax;
     if (i == a.nb - 1) {
       a.dist[size_t(a.nb) * n + k] = dv;
       a.errors[size_t(a.nb) * n + k] = ev;

@@ -21,6 +21,7 @@ def mesh_error_deboor(ode_name: str, mode: str, traj, blocked: bool = False, dev
     xv, uv, pv = _lib.ode_sizes(ode_name)
     if T.ndim != 2 or T.shape[1] != xv + 1 + uv + pv:
         raise ValueError(f"trajectory rows must have {xv + 1 + uv + pv} columns [x,t,u,p]")
+    blocked = bool(blocked) and uv > 0      # without controls there is nothing to hold constant (jit.ensure_kernel registers this form)
     cs = 2 if mode == "Trapezoidal" else _lib.MODES[mode]
     nb = (T.shape[0] - 1) // (cs - 1)
     tsnd = np.empty(nb + 1)

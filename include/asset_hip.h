@@ -355,7 +355,8 @@ int asset_hip_jit_compile(const char* source, const char* functor, int kind, int
 int asset_hip_jit_plugin(const char* name, const char* source, const char* functor, int kind, int mode, int blocked,
                          int seg_per_group, const char* const* options, int noptions, const char* cache_path);
 /* collocation weight tables: which in {"tc","s","A","B","U","C","D","E"}; out receives cs or (cs-1) or
- * (cs-1)*cs doubles (row = interior point).  Returns the count written or <0. */
+ * (cs-1)*cs doubles (row = interior point).  "mesh" (and, with cs = 2, "mesh_trapezoidal"): the scheme of the
+ * mesh-error estimator as order, error weight, factorial, xw[cs], dxw[cs].  Returns the count written or <0. */
 int asset_hip_lgl_table(int cs, const char* which, double* out, int cap);
 int asset_hip_device_count(void);
 const char* asset_hip_last_error(void);

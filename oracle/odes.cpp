@@ -80,6 +80,7 @@ AD2_ODE(cannon_energy, 1, 0, 0)
 AD2_ODE(integrand_lq, 1, 0, 0)
 AD2_ODE(integrand_lq_pi, 1, 0, 0)
 AD2_ODE(lq1, 1, 1, 0)
+AD2_ODE(integrator, 1, 1, 0)
 AD2_ODE(delta3_1, 7, 3, 0)
 AD2_ODE(delta3_2, 7, 3, 0)
 AD2_ODE(delta3_3, 7, 3, 0)
@@ -143,6 +144,7 @@ GEN_DECL(cannon_energy)
 GEN_DECL(integrand_lq)
 GEN_DECL(integrand_lq_pi)
 GEN_DECL(lq1)
+GEN_DECL(integrator)
 GEN_DECL(delta3_1)
 GEN_DECL(delta3_2)
 GEN_DECL(delta3_3)
@@ -237,6 +239,7 @@ int oracle_get_ode4(const oracle_ode* ode, oracle_ode4* out) {
   TRY4(integrand_lq)
   TRY4(integrand_lq_pi)
   TRY4(lq1)
+  TRY4(integrator)
   TRY4(delta3_1)
   TRY4(delta3_2)
   TRY4(delta3_3)
@@ -287,6 +290,7 @@ int oracle_get_ode(const char* name, int provider, oracle_ode* out) {
   TRY(integrand_lq, 1, 0, 0, nullptr)
   TRY(integrand_lq_pi, 1, 0, 0, nullptr)
   TRY(lq1, 1, 1, 0, nullptr)
+  TRY(integrator, 1, 1, 0, nullptr)
   TRY(delta3_1, 7, 3, 0, nullptr)
   TRY(delta3_2, 7, 3, 0, nullptr)
   TRY(delta3_3, 7, 3, 0, nullptr)

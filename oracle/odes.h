@@ -348,6 +348,10 @@ template <class S>
 void integrand_lq_pi(const S* y, S* f, const void*) { f[0] = M_PI * (y[1] * y[1] + y[0] * y[1] + 1.25 * (y[0] * y[0])); }
 template <class S>
 void lq1(const S* y, S* f, const void*) { f[0] = 0.5 * y[0] + y[2]; }
+// integrator: x' = u (1, 1, 0) -- with u = P'(t) at the nodes x = P(t) is an exact solution: the polynomial known answers of the
+// trajectory table and of the mesh-error estimate (tests/interp_checker.py: make_integrator_ode is the same right-hand side in the DSL)
+template <class S>
+void integrator(const S* y, S* f, const void*) { f[0] = y[2]; }
 template <class S>
 void integrand_powp(const S* y, S* f, const void*) {
   f[0] = y[3] * y[0] * y[0] + sin(y[1]) * y[2] + exp(-(y[0] * y[2])) / (1.0 + y[3] * y[3]);

@@ -20,7 +20,9 @@ import subprocess
 import numpy as np
 import pytest
 
+import interp_checker as ick
 import kkt_harness as kh
+import mesh_checker as mck
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 REFERENCE_OBJECTIVE, REFERENCE_TOLERANCE = 58.83219229674185, 0.1       # test_AdaptiveMesh/test_CartPole.py:38-39
@@ -106,6 +108,12 @@ def test_device_loop_converges_to_the_reference_objective(oracle, shim, mode):
     t_o, e_o, d_o = oracle.mesh_error_deboor(ode, oracle.MODES[mode], np.asarray(ph.ActiveTraj), False)
     t_d, e_d, d_d = ph.get_meshinfo_deboor()
     assert np.abs(t_d - t_o).max() < 1e-14 and np.abs(e_d - e_o).max() < 1e-9 * max(1.0, np.abs(e_o).max()) + 1e-12
+    # (that is a 1 % check, the errors of a converged mesh being about 1e-7: on top of it every entry is held to the bound of its own block and state -- two float64 codes,
+    #  2 tau; tests/mesh_checker.py)
+    traj = np.asarray(ph.ActiveTraj)
+    w = mck.compare_float64_codes((t_d, e_d, d_d), (t_o, e_o, d_o), traj, mode, False, 4, 1, ick.oracle_rhs(oracle, "cartpole"),
+                                  mck.eps_f("cartpole"), what=f"cartpole {mode}")
+    print(f"cartpole {mode} x{ph.numDefects}: worst |device - oracle| / (2 tau): tsnd {w[0]:.3f}, mesh_errors {w[1]:.3f}, mesh_dist {w[2]:.3f}")
 
 
 @pytest.mark.gpu

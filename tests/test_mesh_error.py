@@ -3,6 +3,8 @@ ODEPhase<DODE>::get_meshinfo_deboor against a known answer (CPU), and the device
 import numpy as np
 import pytest
 
+import interp_checker as ick
+import mesh_checker as mck
 from asset_asrl_amd import synth
 from helpers import make_vanderpol
 
@@ -40,10 +42,17 @@ def test_device_estimator_matches_oracle(oracle, ode, mode, nseg, blocked):
     traj = synth.make_traj(ode, mode, nseg)
     tsnd, err, dist, emax, dmax = mesh.mesh_error_deboor(ode, mode, traj, blocked)
     rt, rerr, rdist = oracle.mesh_error_deboor(oracle.get_ode(ode, 0), oracle.MODES[mode], traj, blocked)
+    # y_i divides O(1) node data by h^Order (1e13 for LGL7 at h = 0.04) and e_i differences the results: every entry is held to the
+    # bound of its own block and state (tests/mesh_checker.py: tau from the sizes of the terms, tsnd to 4 u) -- one tau, although both
+    # sides are float64 codes
+    xv, uv, _ = synth.ODE_SIZES[ode]
+    mck.compare_float64_codes((tsnd, err, dist), (rt, rerr, rdist), traj, mode, blocked, xv, uv, ick.oracle_rhs(oracle, ode),
+                              mck.eps_f(ode), what=f"{ode} {mode}", factor=1.0)
     np.testing.assert_allclose(tsnd, rt, rtol=0, atol=1e-14)
-    # y_i divides O(1) node data by h^Order (1e13 for LGL7 at h = 0.04): compare relative to each column's size
     for got, ref in ((err, rerr), (dist, rdist)):
         assert np.abs(got - ref).max() <= 1e-9 * np.abs(ref).max()
+    np.testing.assert_array_equal(emax, np.abs(err).max(axis=0))         # the maxima of the device's own columns, bit for bit
+    np.testing.assert_array_equal(dmax, np.abs(dist).max(axis=0))
     np.testing.assert_allclose(emax, np.abs(rerr).max(axis=0), rtol=1e-9)
     np.testing.assert_allclose(dmax, np.abs(rdist).max(axis=0), rtol=1e-9)
 
@@ -56,6 +65,8 @@ def test_phase_mesh_info_with_user_ode(oracle):
     tsnd, err, dist = ph.get_meshinfo_deboor()
     rt, rerr, rdist = oracle.mesh_error_deboor(oracle.get_ode("vanderpol", 0), oracle.MODES["LGL5"], ph.ActiveTraj)
     assert np.abs(err - rerr).max() <= 1e-9 * np.abs(rerr).max()
+    mck.compare_float64_codes((tsnd, err, dist), (rt, rerr, rdist), ph.ActiveTraj, "LGL5", False, 2, 1, ick.oracle_rhs(oracle, "vanderpol"),
+                              mck.eps_f("vanderpol"), what="vanderpol LGL5", factor=1.0)
     t2, bins, error = ph.getMeshInfo(False, 12)
     assert bins.shape == (13,) and bins[0] == 0.0 and bins[-1] == 1.0 and np.all(np.diff(bins) > 0)
     np.testing.assert_allclose(error, np.abs(rerr).max(axis=0), rtol=1e-9)
