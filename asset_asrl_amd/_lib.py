@@ -33,6 +33,12 @@ class PlanStep(C.Structure):
                 ("extra_arg", C.c_int), ("group", C.c_int)]
 
 
+class IntegOptions(C.Structure):
+    """asset_hip_integ_options"""
+    _fields_ = [("def_step", C.c_double), ("min_step", C.c_double), ("max_step", C.c_double), ("max_step_change", C.c_double),
+                ("adaptive", C.c_int), ("max_steps", C.c_int), ("abs_tols", _dp), ("rel_tols", _dp)]
+
+
 class LaunchPlan(C.Structure):
     _fields_ = [("nsteps", C.c_int), ("units_gp", C.c_int), ("step", PlanStep * 3)]
 
@@ -79,6 +85,9 @@ SYMBOLS = {
     "asset_hip_sharded_set_kkt_map": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_longlong]),
     "asset_hip_sharded_eval_assembled": (C.c_int, [C.c_void_p, C.c_int, _dp, _dp, _dp, _dp, _dp]),
     "asset_hip_mesh_error_deboor": (C.c_int, [C.c_char_p, C.c_int, C.c_int, _dp, C.c_int, _dp, _dp, _dp, _dp, _dp, C.c_int]),
+    "asset_hip_mesh_error_integrator": (C.c_int, [C.c_char_p, C.c_int, C.c_int, _dp, C.c_int, C.POINTER(IntegOptions), _dp, _dp, _dp, _dp, _dp,
+                                                 _dp, _ip, _ip, C.c_int]),
+    "asset_hip_rk_table": (C.c_int, [C.c_char_p, _dp, C.c_int]),
     "asset_hip_traj_table_create": (C.c_int, [C.c_char_p, C.c_int, C.c_int, _dp, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
     "asset_hip_traj_table_interp": (C.c_int, [C.c_void_p, _dp, C.c_longlong, C.c_int, _dp, _dp, C.POINTER(C.c_longlong)]),
     "asset_hip_traj_table_interp_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_longlong, C.c_int, C.c_void_p, C.c_void_p,
@@ -193,6 +202,17 @@ def lgl_table(cs: int, which: str) -> np.ndarray:
         check(n, "asset_hip_lgl_table")
     out = buf[:n].copy()
     return out.reshape(cs - 1, cs) if which in "ABUCD" else out
+
+
+def rk_table(which: str) -> np.ndarray:
+    """The Runge-Kutta tableau of the integrator-based mesh-error estimator (csrc/rk_tables.h): "a" [12, 12], "c" [12], "b" [13],
+    "bhat" [13]."""
+    buf = np.zeros(144)
+    n = lib().asset_hip_rk_table(which.encode(), buf.ctypes.data_as(_dp), buf.size)
+    if n < 0:
+        check(n, "asset_hip_rk_table")
+    out = buf[:n].copy()
+    return out.reshape(12, 12) if which == "a" else out
 
 
 def device_count() -> int:

@@ -891,6 +891,91 @@ int asset_hip_mesh_error_deboor(const char* ode, int mode, int blocked, const do
   return 0;
 }
 
+// The integrator-based estimate (integ_kernels.h).  Every input is checked before the device is touched.
+int asset_hip_mesh_error_integrator(const char* ode, int mode, int blocked, const double* traj, int nnodes,
+                                    const asset_hip_integ_options* opt, double* tsnd, double* mesh_errors, double* mesh_dist,
+                                    double* error_max, double* dist_max, double* xend, int* steps, int* status, int device) {
+  if (!ode || !traj || !tsnd || !mesh_errors || !mesh_dist) return fail(ASSET_HIP_EINVAL, "null argument");
+  const asset_hip::KernelEntry* ke = find_entry(ode, mode, blocked);
+  if (!ke) return fail(ASSET_HIP_ENOODE, std::string("no device code compiled for ode='") + ode + "' in this mode");
+  if (ke->table->meta[asset_hip::MF_KIND] != 1 || !asset_hip::entry_has_integ(ke))
+    return fail(ASSET_HIP_EINVAL, "this entry is not a transcription of an ODE");
+  const int K = asset_hip::interp_basis(mode).cs - 1, n = ke->xv, N = ke->xv + 1 + ke->uv + ke->pv;
+  if (nnodes < 2 || (nnodes - 1) % K != 0)
+    return fail(ASSET_HIP_EINVAL, "the trajectory must hold nb*(cs-1)+1 nodes with nb >= 1 blocks");
+  const int nb = (nnodes - 1) / K, nint = nnodes - 1;
+  const double dirn = traj[size_t(nnodes - 1) * N + n] - traj[n];
+  for (int j = 0; j + 1 < nnodes; j++) {
+    const double d = traj[size_t(j + 1) * N + n] - traj[size_t(j) * N + n];
+    if (d == 0.0) return fail(ASSET_HIP_EINVAL, "the trajectory holds duplicate times (node " + std::to_string(j) + ")");
+    if ((d > 0.0) != (dirn > 0.0)) return fail(ASSET_HIP_EINVAL, "the trajectory's times are not monotonic (node " + std::to_string(j) + ")");
+  }
+  // the reference's phase defaults (ODEPhase.h:49; Integrator.h:172, 297-310)
+  asset_hip::IntegOptions o{0.01, 0.01 / 10000, 0.01 * 10000, 3.0, 1, 100000};
+  if (opt) o = asset_hip::IntegOptions{opt->def_step, opt->min_step, opt->max_step, opt->max_step_change, opt->adaptive != 0, opt->max_steps};
+  if (!(o.def_step > 0.0) || !(o.min_step > 0.0) || !(o.max_step > 0.0)) return fail(ASSET_HIP_EINVAL, "step sizes must be positive");
+  if (o.min_step > o.def_step || o.def_step > o.max_step) return fail(ASSET_HIP_EINVAL, "step sizes must satisfy min <= def <= max");
+  if (!(o.max_step_change > 0.0)) return fail(ASSET_HIP_EINVAL, "max_step_change must be positive");
+  if (o.max_steps < 1) return fail(ASSET_HIP_EINVAL, "max_steps must be at least 1");
+  if (const int rc = use_device(device, "no HIP device visible: the estimator has no CPU fallback")) return rc;
+  // one allocation of doubles: traj | abs | rel | xend | e | tsnd | errors | dist | error_max | dist_max | max_err; one of ints: steps | status
+  const size_t sz_traj = size_t(nnodes) * N, sz_x = size_t(nint) * n, sz_e = size_t(nb + 1) * n;
+  const size_t total = sz_traj + 2 * size_t(n) + 2 * sz_x + (nb + 1) + 2 * sz_e + 2 * size_t(nb + 1) + 1;
+  DeviceBuffer<double> buf;
+  DeviceBuffer<int> ibuf;
+  HIP_TRY(buf.allocate(total));
+  HIP_TRY(ibuf.allocate(size_t(nint) * 3));
+  asset_hip::IntegArgs a;
+  a.nb = nb, a.opt = o;
+  double* p = buf.get();
+  a.traj = p, p += sz_traj;
+  double* d_tols = p;   // abs | rel
+  a.abs_tols = p, p += n;
+  a.rel_tols = p, p += n;
+  a.xend = p, p += sz_x;
+  a.e = p, p += sz_x;
+  a.tsnd = p, p += nb + 1;
+  a.errors = p, p += sz_e;
+  a.dist = p, p += sz_e;
+  a.error_max = p, p += nb + 1;
+  a.dist_max = p, p += nb + 1;
+  a.max_err = reinterpret_cast<unsigned long long*>(p);
+  a.steps = ibuf.get(), a.status = ibuf.get() + size_t(nint) * 2;
+  std::vector<double> tols(2 * size_t(n));
+  for (int k = 0; k < n; k++) {
+    tols[k] = (opt && opt->abs_tols) ? opt->abs_tols[k] : 1.0e-12;
+    tols[n + k] = (opt && opt->rel_tols) ? opt->rel_tols[k] : 0.0;
+  }
+  HIP_TRY_AS(hipMemcpy(buf.get(), traj, sz_traj * sizeof(double), hipMemcpyHostToDevice), "hipMemcpy(traj)");
+  HIP_TRY_AS(hipMemcpy(d_tols, tols.data(), tols.size() * sizeof(double), hipMemcpyHostToDevice), "hipMemcpy(tolerances)");
+  HIP_TRY_AS(asset_hip::entry_integ(ke, a, nullptr), "integrator mesh-error kernels");
+  HIP_TRY_AS(hipDeviceSynchronize(), "integrator mesh-error kernels");
+  HIP_TRY_AS(hipMemcpy(tsnd, a.tsnd, (nb + 1) * sizeof(double), hipMemcpyDeviceToHost), "hipMemcpy(results)");
+  HIP_TRY_AS(hipMemcpy(mesh_errors, a.errors, sz_e * sizeof(double), hipMemcpyDeviceToHost), "hipMemcpy(results)");
+  HIP_TRY_AS(hipMemcpy(mesh_dist, a.dist, sz_e * sizeof(double), hipMemcpyDeviceToHost), "hipMemcpy(results)");
+  if (error_max) HIP_TRY_AS(hipMemcpy(error_max, a.error_max, (nb + 1) * sizeof(double), hipMemcpyDeviceToHost), "hipMemcpy(error_max)");
+  if (dist_max) HIP_TRY_AS(hipMemcpy(dist_max, a.dist_max, (nb + 1) * sizeof(double), hipMemcpyDeviceToHost), "hipMemcpy(dist_max)");
+  if (xend) HIP_TRY_AS(hipMemcpy(xend, a.xend, sz_x * sizeof(double), hipMemcpyDeviceToHost), "hipMemcpy(xend)");
+  if (steps) HIP_TRY_AS(hipMemcpy(steps, a.steps, size_t(nint) * 2 * sizeof(int), hipMemcpyDeviceToHost), "hipMemcpy(steps)");
+  if (status) HIP_TRY_AS(hipMemcpy(status, a.status, size_t(nint) * sizeof(int), hipMemcpyDeviceToHost), "hipMemcpy(status)");
+  return 0;
+}
+
+int asset_hip_rk_table(const char* which, double* out, int n) {
+  if (!which || !out) return fail(ASSET_HIP_EINVAL, "bad rk table query");
+  const asset_hip::RkTab& t = asset_hip::h_rk_tab;
+  const double* src = nullptr;
+  int cnt = 0;
+  if (!std::strcmp(which, "a")) src = &t.a[0][0], cnt = 144;
+  else if (!std::strcmp(which, "c")) src = t.c, cnt = 12;
+  else if (!std::strcmp(which, "b")) src = t.b, cnt = 13;
+  else if (!std::strcmp(which, "bhat")) src = t.bhat, cnt = 13;
+  else return fail(ASSET_HIP_EINVAL, "unknown table name");
+  if (n < cnt) return fail(ASSET_HIP_EINVAL, "output buffer too small");
+  for (int i = 0; i < cnt; i++) out[i] = src[i];
+  return cnt;
+}
+
 // ---------------------------------------------------------------------------------------------- trajectory table
 
 struct asset_hip_traj_table {

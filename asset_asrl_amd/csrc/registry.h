@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "kernel_meta.h"
+#include "integ_kernels.h"
 #include "interp_kernels.h"
 #include "mesh_kernels.h"
 
@@ -170,6 +171,9 @@ inline hipError_t klaunch(const KRef& k, dim3 grid, dim3 block, size_t shmem, hi
   X(K_MESH_ERROR, NONE, true, mesh_error_kernel, 0)                                                                             \
   X(K_INTERP_XDOT, LGL, true, interp_xdot_kernel)                                                                               \
   X(K_INTERP_EVAL, LGL, true, interp_eval_kernel)                                                                               \
+  /* integrator-based mesh error (integ_kernels.h): every node interval integrated again, the per-block estimate */             \
+  X(K_INTEG_STEP, LGL, true, integ_reintegrate_kernel)                                                                          \
+  X(K_INTEG_ERROR, NONE, true, integ_mesh_error_kernel, 0)                                                                      \
   /* plain functions and bundles of them (func_kernels.h) */                                                                    \
   X(K_FUNC0, FUNC, true, func_kernel, 0, false)                                                                                 \
   X(K_FUNC1, FUNC, true, func_kernel, 1, false)                                                                                 \
@@ -503,6 +507,24 @@ inline hipError_t entry_mesh(const KernelEntry* ke, const MeshArgs& a, hipStream
   double order = sc.order, weight = sc.error_weight;
   void* eargs[] = {&args, &xv, &order, &weight};
   return klaunch(ke->table->k[K_MESH_ERROR], dim3(grid), dim3(64), 0, st, eargs);
+}
+
+// integrator-based mesh-error estimate (integ_kernels.h); only transcriptions of an ODE have it.  `a.max_err` is zeroed here: the
+// lanes of stage 1 raise it
+inline bool entry_has_integ(const KernelEntry* ke) { return bool(ke->table->k[K_INTEG_STEP]) && bool(ke->table->k[K_INTEG_ERROR]); }
+inline hipError_t entry_integ(const KernelEntry* ke, const IntegArgs& a, hipStream_t st) {
+  IntegArgs args = a;
+  const int K = interp_basis(ke->mode).cs - 1, lanes = integ_lanes(ke->xv);
+  const long long nint = (long long)a.nb * K;
+  hipError_t e = hipMemsetAsync(a.max_err, 0, sizeof(unsigned long long), st);
+  if (e != hipSuccess) return e;
+  void* sargs[] = {&args};
+  e = klaunch(ke->table->k[K_INTEG_STEP], dim3(unsigned((nint + lanes - 1) / lanes)), dim3(64), 0, st, sargs);
+  if (e != hipSuccess) return e;
+  int n = ke->xv, N = ke->xv + 1 + ke->uv + ke->pv, k = K;
+  double order = mesh_scheme(ke->mode).order;
+  void* eargs[] = {&args, &n, &N, &k, &order};
+  return klaunch(ke->table->k[K_INTEG_ERROR], dim3((a.nb + 63) / 64), dim3(64), 0, st, eargs);
 }
 
 // trajectory table (interp_kernels.h); only transcriptions of an ODE have it.  entry_interp_table: stage 1 (a.traj -> a.xdot, a.tb),

@@ -8,6 +8,7 @@
 // kernels), so the list does not depend on the shape.
 #pragma once
 #include "kernel_meta.h"
+#include "integ_kernels.h"
 #include "interp_kernels.h"
 #include "mesh_kernels.h"
 

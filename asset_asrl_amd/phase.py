@@ -105,6 +105,9 @@ class Phase:
         self.AdaptiveMesh, self.MeshConverged, self.MeshIters = False, False, []
         self.MeshTol, self.MaxMeshIters, self.MaxSegments, self.MinSegments, self.NumExtraSegs = 1.0e-6, 10, 10000, 4, 4
         self.MeshRedFactor, self.MeshIncFactor, self.MeshErrFactor, self.MeshErrorCriteria = 0.5, 5.0, 10.0, "max"
+        self.MeshErrorEstimator = "deboor"      # or "integrator": setMeshErrorEstimator (ODEPhaseBase.h:117)
+        from .mesh import IntegratorOptions
+        self.integrator = IntegratorOptions(ode.XVars())   # the re-integrator's settings (ODEPhase.h:42, 49)
         self.XtUPUnits = np.ones(ode.XtUPVars())
         self._ode_scaled = None
         self._eq_funcs = []       # (region, func, xtuv, opv, spv) -- addEqualCon
@@ -621,12 +624,30 @@ class Phase:
             dist = dist * (ut ** (order + 1) / ux) ** (1.0 / (order + 1))
         return tsnd, err, dist
 
-    def getMeshInfo(self, integ: bool = False, n: int = 100):
-        """(tsnd, bins, error) -- ODEPhaseBase.h:1355-1399; only the de Boor estimator is provided."""
-        if integ:
-            raise NotImplementedError("the integrator-based estimator needs the ODE integrator, which stays on the host")
+    def get_meshinfo_integrator(self):
+        """(tsnd, mesh_errors[XV, nb+1], mesh_dist[XV, nb+1]) -- ODEPhase.h:592-685: every node interval of the active trajectory
+        integrated again (csrc/integ_kernels.h) with the settings of ``self.integrator``.  With AutoScaling the scaled ODE is integrated
+        over ActiveTraj / XtUPUnits, as ODEPhase.h:671-678 does."""
         from . import mesh
-        tsnd, err, dist = self.get_meshinfo_deboor()
+        name = jit.ensure_kernel(self._active_ode(), self.TranscriptionMode, self._blocked())
+        traj = self.ActiveTraj / self.XtUPUnits if self.AutoScaling else self.ActiveTraj
+        return mesh.mesh_error_integrator(name, self.TranscriptionMode, traj, self._blocked(), self.integrator, self.device)[:3]
+
+    def setMeshErrorEstimator(self, name: str):
+        """The estimator checkMesh uses: "deboor" (the default) or "integrator"; checkMesh refuses any other name (ODEPhaseBase.cpp:1452-1458)."""
+        self.MeshErrorEstimator = name
+
+    def _meshinfo(self):
+        if self.MeshErrorEstimator == "integrator":
+            return self.get_meshinfo_integrator()
+        if self.MeshErrorEstimator == "deboor":
+            return self.get_meshinfo_deboor()
+        raise ValueError("Unknown mesh error estimator")
+
+    def getMeshInfo(self, integ: bool = False, n: int = 100):
+        """(tsnd, bins, error) -- ODEPhaseBase.h:1355-1399, with the integrator-based or the de Boor estimator."""
+        from . import mesh
+        tsnd, err, dist = self.get_meshinfo_integrator() if integ else self.get_meshinfo_deboor()
         return mesh.bins_from_density(tsnd, np.abs(err).max(axis=0), np.abs(dist).max(axis=0), n)
 
     # ---- the adaptive mesh loop's two steps (ODEPhaseBase.cpp:1443-1494 checkMesh, :1496-1542 updateMesh).  The solver between
@@ -638,14 +659,14 @@ class Phase:
         self.MeshTol = abs(float(tol))
 
     def checkMesh(self, meshinfo=None) -> bool:
-        """Estimate the error of the active trajectory (the device de Boor estimator; `meshinfo`: another source of
+        """Estimate the error of the active trajectory (the device estimator MeshErrorEstimator names; `meshinfo`: another source of
         (tsnd, mesh_errors[XV, nb+1], mesh_dist[XV, nb+1]) -- a test's oracle), record the iterate and compare the criterion
         ("max", "avg", "geometric": MeshIterateInfo.h:42-47) with MeshTol."""
         from .mesh import MeshIterateInfo
-        tsnd, err, dist = meshinfo() if meshinfo is not None else self.get_meshinfo_deboor()
+        tsnd, err, dist = meshinfo() if meshinfo is not None else self._meshinfo()
         it = MeshIterateInfo(self.numDefects, self.MeshTol, tsnd, np.abs(err).max(axis=0), np.abs(dist).max(axis=0))
         if self.MeshErrorCriteria not in ("max", "avg", "geometric"):
-            raise ValueError("Unknown mesh error criteria")      # ("endtoend" needs the integrator, which stays on the host)
+            raise ValueError("Unknown mesh error criteria")      # ("endtoend" is one serial integration of the whole phase: not built)
         crit = {"max": it.max_error, "avg": it.avg_error, "geometric": it.gmean_error}[self.MeshErrorCriteria]
         it.converged = self.MeshConverged = bool(crit < self.MeshTol)
         self.MeshIters.append(it)

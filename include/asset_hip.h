@@ -298,6 +298,33 @@ int asset_hip_defect_time_device(asset_hip_defect_t h, int what, const double* d
 int asset_hip_mesh_error_deboor(const char* ode, int mode, int blocked, const double* traj, int nnodes, double* tsnd,
                                 double* mesh_errors, double* mesh_dist, double* error_max, double* dist_max, int device);
 
+/* ---- integrator-based mesh-error estimate ----
+ * Replaces ODEPhase<DODE>::get_meshinfo_integrator (OptimalControl/ODEPhase.h:592-685), the estimator behind checkMesh / getMeshInfo
+ * when MeshErrorEstimator == "integrator": the ODE is integrated again across every node interval with the Prince-Dormand 8(7) pair
+ * (Integrators/Integrator.h:536-676) -- controls from the block's own polynomial, or held at the start node's for ODEs without
+ * controls and with `blocked` --, e = |integrated state - next node| per interval, and per block the time-weighted sum of its
+ * intervals' e (mesh_errors) and (mesh_errors / (|h|^(Order+1) max e))^(1/(Order+1)) (mesh_dist).  traj, tsnd, mesh_errors, mesh_dist,
+ * error_max, dist_max: as asset_hip_mesh_error_deboor, with nb >= 1.  Optional details per node interval: xend[nnodes-1][XV] the
+ * integrated end states, steps[nnodes-1][2] accepted and rejected steps, status[nnodes-1]: 0 ok, 1 the interval took max_steps steps
+ * (accepted + rejected) without arriving, 2 the step, the state or the interval's own rows stopped being finite; xend is NaN where
+ * status != 0 (and so are the estimates that depend on it).  opt == NULL: the reference's phase defaults -- def_step 0.01, min_step
+ * def / 1e4, max_step def * 1e4, max_step_change 3, adaptive, max_steps 100000, abs_tols 1e-12, rel_tols 0.
+ * Errors: ASSET_HIP_ENOODE; ASSET_HIP_EINVAL (nb < 1, nnodes != nb (cs-1) + 1, duplicate or non-monotonic times, a step size or
+ * max_step_change <= 0, min_step > def_step, def_step > max_step, max_steps < 1); ASSET_HIP_ENODEV.  Nothing is written on an error. */
+typedef struct {
+  double def_step, min_step, max_step, max_step_change;
+  int adaptive;
+  int max_steps;
+  const double* abs_tols; /* [XV] each; NULL: 1e-12 / 0 */
+  const double* rel_tols;
+} asset_hip_integ_options;
+int asset_hip_mesh_error_integrator(const char* ode, int mode, int blocked, const double* traj, int nnodes,
+                                    const asset_hip_integ_options* opt, double* tsnd, double* mesh_errors, double* mesh_dist,
+                                    double* error_max, double* dist_max, double* xend, int* steps, int* status, int device);
+/* The Runge-Kutta tableau of the estimator (host copy of csrc/rk_tables.h): which = "a" (12 x 12, row s-1 = stage s), "c" (12),
+ * "b" (13, order 8, propagated), "bhat" (13, order 7).  Returns the count written or <0. */
+int asset_hip_rk_table(const char* which, double* out, int n);
+
 /* ---- trajectory table: the transcription's own Hermite interpolant of a phase trajectory, on the device ----
  * Replaces LGLInterpTable for exact data (OptimalControl/LGLInterpTable.h:349-372, 480-669, 866-926), the table behind
  * ODEPhaseBase::refineTrajManual / updateMesh / returnTrajRange / returnTrajRangeND / returnTrajTable
