@@ -87,6 +87,11 @@ SYMBOLS = {
     "asset_hip_mesh_error_deboor": (C.c_int, [C.c_char_p, C.c_int, C.c_int, _dp, C.c_int, _dp, _dp, _dp, _dp, _dp, C.c_int]),
     "asset_hip_mesh_error_integrator": (C.c_int, [C.c_char_p, C.c_int, C.c_int, _dp, C.c_int, C.POINTER(IntegOptions), _dp, _dp, _dp, _dp, _dp,
                                                  _dp, _ip, _ip, C.c_int]),
+    "asset_hip_propagate": (C.c_int, [C.c_char_p, _dp, C.c_longlong, _dp, C.c_int, C.POINTER(IntegOptions), _dp, _ip, _ip, C.c_int]),
+    "asset_hip_propagate_stm": (C.c_int, [C.c_char_p, _dp, C.c_longlong, _dp, C.POINTER(IntegOptions), _dp, _dp, _ip, _ip, C.c_int]),
+    "asset_hip_propagate_stm_lanes": (C.c_int, [C.c_char_p, _dp, C.c_longlong, _dp, C.POINTER(IntegOptions), _dp, _dp, _ip, _ip, _dp,
+                                               C.c_int]),
+    "asset_hip_propagate_plan": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_longlong, C.c_int, C.POINTER(C.c_longlong)]),
     "asset_hip_rk_table": (C.c_int, [C.c_char_p, _dp, C.c_int]),
     "asset_hip_traj_table_create": (C.c_int, [C.c_char_p, C.c_int, C.c_int, _dp, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
     "asset_hip_traj_table_interp": (C.c_int, [C.c_void_p, _dp, C.c_longlong, C.c_int, _dp, _dp, C.POINTER(C.c_longlong)]),
@@ -213,6 +218,14 @@ def rk_table(which: str) -> np.ndarray:
         check(n, "asset_hip_rk_table")
     out = buf[:n].copy()
     return out.reshape(12, 12) if which == "a" else out
+
+
+def propagate_plan(xv: int, uv: int, pv: int, m: int, stm: bool):
+    """dict(group, lanes, passes, problems_per_wg, lds_bytes, grid, columns): what a batched propagation of these sizes launches
+    (csrc/capi/propagate_plan.h through asset_hip_propagate_plan -- no device)."""
+    out = (C.c_longlong * 7)()
+    check(lib().asset_hip_propagate_plan(int(xv), int(uv), int(pv), int(m), int(bool(stm)), out), "asset_hip_propagate_plan")
+    return dict(zip(("group", "lanes", "passes", "problems_per_wg", "lds_bytes", "grid", "columns"), [int(v) for v in out]))
 
 
 def device_count() -> int:

@@ -23,6 +23,7 @@
 #include "registry.h"
 #include "capi/kkt_map.h"
 #include "capi/owners.h"
+#include "capi/propagate_plan.h"
 
 namespace asset_hip {
 // values[loc[l]] = sum of stage[ptr[l] .. ptr[l+1]) in a FIXED order: thread t of the block adds cells t, t+256, ... in
@@ -958,6 +959,109 @@ int asset_hip_mesh_error_integrator(const char* ode, int mode, int blocked, cons
   if (xend) HIP_TRY_AS(hipMemcpy(xend, a.xend, sz_x * sizeof(double), hipMemcpyDeviceToHost), "hipMemcpy(xend)");
   if (steps) HIP_TRY_AS(hipMemcpy(steps, a.steps, size_t(nint) * 2 * sizeof(int), hipMemcpyDeviceToHost), "hipMemcpy(steps)");
   if (status) HIP_TRY_AS(hipMemcpy(status, a.status, size_t(nint) * sizeof(int), hipMemcpyDeviceToHost), "hipMemcpy(status)");
+  return 0;
+}
+
+// ---------------------------------------------------------------------------------------------- batched propagation
+namespace {
+// the one entry of an ODE that holds its propagation kernels (registry.h: prop_home)
+const asset_hip::KernelEntry* prop_entry(const char* ode) {
+  const asset_hip::KernelEntry* ke = find_entry(ode, asset_hip::PROP_HOME_MODE, 0);
+  return (ke && asset_hip::prop_home(ke->mode, ke->blocked != 0) && ke->table->meta[asset_hip::MF_KIND] == 1 && asset_hip::entry_has_prop(ke)) ? ke : nullptr;
+}
+
+// the option rules of asset_hip_mesh_error_integrator
+int integ_options_checked(const asset_hip_integ_options* opt, asset_hip::IntegOptions& o) {
+  o = asset_hip::IntegOptions{0.01, 0.01 / 10000, 0.01 * 10000, 3.0, 1, 100000};
+  if (opt) o = asset_hip::IntegOptions{opt->def_step, opt->min_step, opt->max_step, opt->max_step_change, opt->adaptive != 0, opt->max_steps};
+  if (!(o.def_step > 0.0) || !(o.min_step > 0.0) || !(o.max_step > 0.0)) return fail(ASSET_HIP_EINVAL, "step sizes must be positive");
+  if (o.min_step > o.def_step || o.def_step > o.max_step) return fail(ASSET_HIP_EINVAL, "step sizes must satisfy min <= def <= max");
+  if (!(o.max_step_change > 0.0)) return fail(ASSET_HIP_EINVAL, "max_step_change must be positive");
+  if (o.max_steps < 1) return fail(ASSET_HIP_EINVAL, "max_steps must be at least 1");
+  return 0;
+}
+
+int propagate_impl(const char* ode, const double* y0, long long m, const double* tf, int ns, const asset_hip_integ_options* opt, bool stm,
+                   double* xs, double* jac, int* steps, int* status, double* xf_last, int device) {
+  if (!ode || !y0 || !tf || !xs || (stm && !jac)) return fail(ASSET_HIP_EINVAL, "null argument");
+  if (m < 1) return fail(ASSET_HIP_EINVAL, "m must be at least 1");
+  if (ns < 1) return fail(ASSET_HIP_EINVAL, "ns must be at least 1");
+  const asset_hip::KernelEntry* ke = prop_entry(ode);
+  if (!ke) return fail(ASSET_HIP_ENOODE, std::string("no propagation kernels compiled for ode='") + ode + "' (its LGL3 entry holds them)");
+  asset_hip::IntegOptions o;
+  if (const int rc = integ_options_checked(opt, o)) return rc;
+  for (long long i = 0; i < m; i++)
+    if (!std::isfinite(tf[i])) return fail(ASSET_HIP_EINVAL, "tf is not finite (problem " + std::to_string(i) + ")");
+  const int n = ke->xv, N = ke->xv + 1 + ke->uv + ke->pv, C = N - 1;
+  const asset_hip::PropPlan plan = asset_hip::propagate_plan(ke->xv, ke->uv, ke->pv, m, stm ? 1 : 0);
+  if (plan.grid < 1 || plan.grid > 0x7fffffffLL || size_t(plan.lds_bytes) > 64 * 1024)
+    return fail(ASSET_HIP_EINVAL, "the batch does not fit one launch (workgroups or LDS)");
+  if (const int rc = use_device(device, "no HIP device visible: the propagation has no CPU fallback")) return rc;
+  // one allocation of doubles: y0 | tf | abs | rel | xs | (stm: S | jac | xlast); one of ints: steps | status
+  const size_t um = size_t(m), sz_y = um * N, sz_x = um * size_t(stm ? 1 : ns) * n;
+  const size_t sz_s = stm ? um * n * C : 0, sz_j = stm ? um * n * (N + 1) : 0, sz_l = stm ? um * n : 0;
+  DeviceBuffer<double> buf;
+  DeviceBuffer<int> ibuf;
+  HIP_TRY(buf.allocate(sz_y + um + 2 * size_t(n) + sz_x + sz_s + sz_j + sz_l));
+  HIP_TRY(ibuf.allocate(um * 3));
+  asset_hip::PropArgs a;
+  a.m = m, a.ns = stm ? 1 : ns, a.opt = o;
+  a.group = plan.group, a.lanes = plan.lanes, a.passes = plan.passes;
+  double* p = buf.get();
+  double* d_y = p;
+  a.y0 = p, p += sz_y;
+  double* d_tf = p;
+  a.tf = p, p += um;
+  double* d_tols = p;
+  a.abs_tols = p, p += n;
+  a.rel_tols = p, p += n;
+  a.xs = p, p += sz_x;
+  a.S = stm ? p : nullptr, p += sz_s;
+  a.jac = stm ? p : nullptr, p += sz_j;
+  a.xlast = stm ? p : nullptr;
+  a.steps = ibuf.get(), a.status = ibuf.get() + um * 2;
+  std::vector<double> tols(2 * size_t(n));
+  for (int k = 0; k < n; k++) {
+    tols[k] = (opt && opt->abs_tols) ? opt->abs_tols[k] : 1.0e-12;
+    tols[n + k] = (opt && opt->rel_tols) ? opt->rel_tols[k] : 0.0;
+  }
+  HIP_TRY_AS(hipMemcpy(d_y, y0, sz_y * sizeof(double), hipMemcpyHostToDevice), "hipMemcpy(y0)");
+  HIP_TRY_AS(hipMemcpy(d_tf, tf, um * sizeof(double), hipMemcpyHostToDevice), "hipMemcpy(tf)");
+  HIP_TRY_AS(hipMemcpy(d_tols, tols.data(), tols.size() * sizeof(double), hipMemcpyHostToDevice), "hipMemcpy(tolerances)");
+  void* kargs[] = {&a};
+  const asset_hip::KernelTable& t = *ke->table;
+  HIP_TRY_AS(asset_hip::klaunch(t.k[stm ? asset_hip::K_PROP_STM : asset_hip::K_PROP_BATCH], dim3(unsigned(plan.grid)), dim3(64),
+                                size_t(plan.lds_bytes), nullptr, kargs), "propagation kernel");
+  if (stm) HIP_TRY_AS(asset_hip::klaunch(t.k[asset_hip::K_PROP_JAC], dim3(unsigned((m + 63) / 64)), dim3(64), 0, nullptr, kargs), "STM assembly kernel");
+  HIP_TRY_AS(hipDeviceSynchronize(), "propagation kernels");
+  HIP_TRY_AS(hipMemcpy(xs, a.xs, sz_x * sizeof(double), hipMemcpyDeviceToHost), "hipMemcpy(states)");
+  if (stm) HIP_TRY_AS(hipMemcpy(jac, a.jac, sz_j * sizeof(double), hipMemcpyDeviceToHost), "hipMemcpy(jac)");
+  if (stm && xf_last) HIP_TRY_AS(hipMemcpy(xf_last, a.xlast, sz_l * sizeof(double), hipMemcpyDeviceToHost), "hipMemcpy(xf_last)");
+  if (steps) HIP_TRY_AS(hipMemcpy(steps, a.steps, um * 2 * sizeof(int), hipMemcpyDeviceToHost), "hipMemcpy(steps)");
+  if (status) HIP_TRY_AS(hipMemcpy(status, a.status, um * sizeof(int), hipMemcpyDeviceToHost), "hipMemcpy(status)");
+  return 0;
+}
+}  // namespace
+
+int asset_hip_propagate(const char* ode, const double* y0, long long m, const double* tf, int ns, const asset_hip_integ_options* opt,
+                        double* xs, int* steps, int* status, int device) {
+  return propagate_impl(ode, y0, m, tf, ns, opt, false, xs, nullptr, steps, status, nullptr, device);
+}
+int asset_hip_propagate_stm(const char* ode, const double* y0, long long m, const double* tf, const asset_hip_integ_options* opt,
+                            double* xf, double* jac, int* steps, int* status, int device) {
+  return propagate_impl(ode, y0, m, tf, 1, opt, true, xf, jac, steps, status, nullptr, device);
+}
+int asset_hip_propagate_stm_lanes(const char* ode, const double* y0, long long m, const double* tf, const asset_hip_integ_options* opt,
+                                  double* xf, double* jac, int* steps, int* status, double* xf_last, int device) {
+  if (!xf_last) return fail(ASSET_HIP_EINVAL, "null argument");
+  return propagate_impl(ode, y0, m, tf, 1, opt, true, xf, jac, steps, status, xf_last, device);
+}
+int asset_hip_propagate_plan(int xv, int uv, int pv, long long m, int stm, long long* out) {
+  if (!out) return fail(ASSET_HIP_EINVAL, "null argument");
+  const asset_hip::PropPlan p = asset_hip::propagate_plan(xv, uv, pv, m, stm);
+  if (p.grid < 1) return fail(ASSET_HIP_EINVAL, "sizes must satisfy xv >= 1, uv >= 0, pv >= 0, m >= 1");
+  const long long v[7] = {p.group, p.lanes, p.passes, p.problems_per_wg, p.lds_bytes, p.grid, p.columns};
+  for (int k = 0; k < 7; k++) out[k] = v[k];
   return 0;
 }
 

@@ -18,6 +18,7 @@
 #include "integ_kernels.h"
 #include "interp_kernels.h"
 #include "mesh_kernels.h"
+#include "propagate_kernels.h"
 
 namespace asset_hip {
 
@@ -114,10 +115,18 @@ inline hipError_t klaunch(const KRef& k, dim3 grid, dim3 block, size_t shmem, hi
 // ---- the kernels of a table: ONE list --------------------------------------------------------------------------------------
 // X(slot, family, condition, kernel template, trailing template arguments...).  The family says what precedes the trailing
 // arguments -- LGLG: <Ode, SCH, BLOCKED, G, ...>, LGL: <Ode, SCH, BLOCKED, ...>, NONE: <...> (all three: transcriptions of an ODE),
+// ODE: <Ode, ...> (kernels of the ODE alone, whatever the transcription: they live in ONE entry per ODE, prop_home below),
 // FUNC: <F, ...> (plain functions), BUNDLE: <..., Fs...> (bundles, run-time modules only) -- and the condition is the compile-time
 // one (D = Dims<Ode, SCH, BLOCKED>) under which a shape linked into the library has the kernel.  The slot enum, the static tables
 // (lgl_static_table, func_static_table) and the name expressions of a run-time module (rtc_kernel_expr, which names every slot of
 // its kind: rtc_device.h compiles the variants a shape lacks to empty kernels) are all generated from this list.
+// The propagation kernels depend on the ODE only.  They are compiled into, and looked up through, exactly one entry per ODE: its
+// LGL3 transcription (id 2) with controls that are not BlockConstant -- every ODE that has any entry can have that one (the smallest
+// scheme; an ODE without controls has no BlockConstant entries at all).  The rule is written here and nowhere else: the static
+// tables, the name expressions of a run-time module and the C ABI's look-up (capi.hip: prop_entry) all call it.
+constexpr int PROP_HOME_MODE = 2;
+constexpr bool prop_home(int sch, bool blocked) { return sch == PROP_HOME_MODE && !blocked; }
+
 #define ASSET_KERNELS(X)                                                                                                        \
   /* defect_kernels.h: ODE stage (S1), dense stage (S2), both in one launch (S3), ... as two-wave workgroups (S4) */            \
   X(K_LGL1_S1, LGLG, true, lgl_defect_kernel, 1, 1, false)                                                                      \
@@ -182,7 +191,11 @@ inline hipError_t klaunch(const KRef& k, dim3 grid, dim3 block, size_t shmem, hi
   X(K_FUNC2_ASM, FUNC, true, func_kernel, 2, true)                                                                              \
   X(K_BUNDLE0, BUNDLE, true, func_bundle_kernel, 0)                                                                             \
   X(K_BUNDLE1, BUNDLE, true, func_bundle_kernel, 1)                                                                             \
-  X(K_BUNDLE2, BUNDLE, true, func_bundle_kernel, 2)
+  X(K_BUNDLE2, BUNDLE, true, func_bundle_kernel, 2)                                                                             \
+  /* batched propagation (propagate_kernels.h): end states and samples, state + STM columns, the STM's assembly */               \
+  X(K_PROP_BATCH, ODE, prop_home(SCH, BLOCKED), prop_batch_kernel)                                                              \
+  X(K_PROP_STM, ODE, prop_home(SCH, BLOCKED), prop_stm_kernel)                                                                  \
+  X(K_PROP_JAC, ODE, prop_home(SCH, BLOCKED), prop_stm_jac_kernel)
 
 #define ASSET_X_ENUM(NAME, ...) NAME,
 enum KSlot : int { ASSET_KERNELS(ASSET_X_ENUM) K_COUNT };
@@ -527,6 +540,12 @@ inline hipError_t entry_integ(const KernelEntry* ke, const IntegArgs& a, hipStre
   return klaunch(ke->table->k[K_INTEG_ERROR], dim3((a.nb + 63) / 64), dim3(64), 0, st, eargs);
 }
 
+// batched propagation (propagate_kernels.h): the ODE's home entry (prop_home) has the three kernels; capi.hip launches them by the
+// plan of capi/propagate_plan.h
+inline bool entry_has_prop(const KernelEntry* ke) {
+  return bool(ke->table->k[K_PROP_BATCH]) && bool(ke->table->k[K_PROP_STM]) && bool(ke->table->k[K_PROP_JAC]);
+}
+
 // trajectory table (interp_kernels.h); only transcriptions of an ODE have it.  entry_interp_table: stage 1 (a.traj -> a.xdot, a.tb),
 // entry_interp: stage 2 (a.times -> a.out, a.dout)
 inline bool entry_has_interp(const KernelEntry* ke) { return bool(ke->table->k[K_INTERP_XDOT]) && bool(ke->table->k[K_INTERP_EVAL]); }
@@ -564,6 +583,7 @@ inline hipError_t entry_lane_setup(const KernelEntry* ke, int level, void* out, 
 #define ASSET_FILL_LGLG(NAME, COND, T, ...) if constexpr (COND) r.k[NAME].host = ASSET_KPTR(T<Ode, SCH, BLOCKED, G, ##__VA_ARGS__>);
 #define ASSET_FILL_LGL(NAME, COND, T, ...) if constexpr (COND) r.k[NAME].host = ASSET_KPTR(T<Ode, SCH, BLOCKED, ##__VA_ARGS__>);
 #define ASSET_FILL_NONE(NAME, COND, T, ...) if constexpr (COND) r.k[NAME].host = ASSET_KPTR(T<__VA_ARGS__>);
+#define ASSET_FILL_ODE(NAME, COND, T, ...) if constexpr (COND) r.k[NAME].host = ASSET_KPTR(T<Ode, ##__VA_ARGS__>);
 #define ASSET_FILL_FUNC(NAME, COND, T, ...)
 #define ASSET_FILL_BUNDLE(NAME, COND, T, ...)
 #define ASSET_X_FILL(NAME, FAMILY, COND, T, ...) ASSET_FILL_##FAMILY(NAME, COND, T, ##__VA_ARGS__)
@@ -581,10 +601,12 @@ const KernelTable* lgl_static_table() {
 #undef ASSET_FILL_LGLG
 #undef ASSET_FILL_LGL
 #undef ASSET_FILL_NONE
+#undef ASSET_FILL_ODE
 #undef ASSET_FILL_FUNC
 #define ASSET_FILL_LGLG(NAME, COND, T, ...)
 #define ASSET_FILL_LGL(NAME, COND, T, ...)
 #define ASSET_FILL_NONE(NAME, COND, T, ...)
+#define ASSET_FILL_ODE(NAME, COND, T, ...)
 #define ASSET_FILL_FUNC(NAME, COND, T, ...) r.k[NAME].host = ASSET_KPTR(T<F, ##__VA_ARGS__>);
 template <class F>
 const KernelTable* func_static_table() {
@@ -599,6 +621,7 @@ const KernelTable* func_static_table() {
 #undef ASSET_FILL_LGLG
 #undef ASSET_FILL_LGL
 #undef ASSET_FILL_NONE
+#undef ASSET_FILL_ODE
 #undef ASSET_FILL_FUNC
 #undef ASSET_FILL_BUNDLE
 #undef ASSET_X_FILL
@@ -636,6 +659,7 @@ inline std::string rtc_kernel_expr(int slot, int kind, const std::string& type, 
 #define ASSET_RTC_LGLG 1, lglg
 #define ASSET_RTC_LGL 1, lgl
 #define ASSET_RTC_NONE 1, none
+#define ASSET_RTC_ODE (prop_home(csv, blocked) ? 1 : 0), type
 #define ASSET_RTC_FUNC 2, type
 #define ASSET_RTC_BUNDLE 3, type, true
 #define ASSET_X_EXPR(NAME, FAMILY, COND, T, ...) case NAME: return expr(#T, #__VA_ARGS__, ASSET_RTC_##FAMILY);
@@ -644,6 +668,7 @@ inline std::string rtc_kernel_expr(int slot, int kind, const std::string& type, 
 #undef ASSET_RTC_LGLG
 #undef ASSET_RTC_LGL
 #undef ASSET_RTC_NONE
+#undef ASSET_RTC_ODE
 #undef ASSET_RTC_FUNC
 #undef ASSET_RTC_BUNDLE
   return "";

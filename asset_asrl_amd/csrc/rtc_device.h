@@ -11,6 +11,7 @@
 #include "integ_kernels.h"
 #include "interp_kernels.h"
 #include "mesh_kernels.h"
+#include "propagate_kernels.h"
 
 #define ASSET_RTC_LGL(ODE, CSV, BLK, G)                                                                            \
   extern "C" __device__ const long long asset_rtc_meta[::asset_hip::MF_COUNT] = {                                  \

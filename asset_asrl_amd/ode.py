@@ -110,6 +110,11 @@ class ODEBase:
             ph.setTraj(traj, nsegs if nsegs is not None else max(len(traj) - 1, 1))
         return ph
 
+    def integrator(self, *args, device: int = 0):
+        """``integrator(def_step)`` / ``integrator("DOPRI87", def_step)``: batched propagation on the device (integrator.py)."""
+        from .integrator import Integrator
+        return Integrator(self, *args, device=device)
+
 
 # =========================================================================== library
 

@@ -325,6 +325,41 @@ int asset_hip_mesh_error_integrator(const char* ode, int mode, int blocked, cons
  * "b" (13, order 8, propagated), "bhat" (13, order 7).  Returns the count written or <0. */
 int asset_hip_rk_table(const char* which, double* out, int n);
 
+/* ---- batched propagation of initial-value problems ----
+ * Replaces Integrator::integrate_parallel / integrate_dense_parallel / integrate_stm_parallel (Integrators/Integrator.h:1788-1832,
+ * 1917-1946, 2071-2130) for an integrator without a controller: m unrelated problems of one ODE, row i of y0[m][XV+1+UV+PV] =
+ * [x0, t0, u, p] integrated to tf[i] with the Prince-Dormand 8(7) pair and the step rule of asset_hip_mesh_error_integrator, controls
+ * and parameters held at the row's (csrc/propagate_kernels.h).  `opt` as there (NULL: the same defaults); max_steps counts the
+ * accepted + rejected steps of one whole propagation.  The kernels belong to the ODE, not to a transcription: any ODE that has an
+ * LGL3 entry without BlockConstant controls has them (run-time ODEs: asset_hip_jit_plugin with mode ASSET_HIP_LGL3, blocked 0).
+ *
+ * asset_hip_propagate: xs[m][ns][XV].  ns == 1: the end states.  ns > 1: sample j is the state at t0 + (j (tf - t0)) / (ns - 1), sample 0
+ * is x0 and the last one is at tf itself; every output time is reached by shortening the step that would pass it (integrator-accurate,
+ * not interpolated; the end state of a dense call is therefore not bitwise that of the ns == 1 call).  steps[m][2] accepted and
+ * rejected steps, status[m]: 0 ok, 1 max_steps reached, 2 the step, a state or the row stopped being finite; a problem whose status
+ * is not 0 has NaN in the samples it did not reach.  tf[i] == t0: the samples are x0, steps 0, 0, status 0.  steps, status may be NULL.
+ *
+ * asset_hip_propagate_stm: xf[m][XV] and jac[m][XV][XV+1+UV+PV+1], row-major, columns [x0 | t0 | u | p | tf] (the reference's IRows + 1
+ * layout).  The x0, u and p columns are the exact derivative of the DISCRETE map -- the accepted step sequence held fixed, what the
+ * reference chains step by step; the t0 and tf columns are the FLOW's: -S_x f(x0, t0, u, p) and f(xf, tf, u, p).  xf is bitwise the
+ * ns == 1 end state of asset_hip_propagate.  asset_hip_propagate_stm_lanes is a diagnostic variant, not needed for results: the same
+ * call with one more output, xf_last[m][XV], the end state as the last lane of the problem's lane group holds it (every lane of a group
+ * integrates the state itself; the tests compare the two).
+ *
+ * asset_hip_propagate_plan (no device): what a call with these sizes launches (csrc/capi/propagate_plan.h) -- out[7] = lanes per
+ * problem G, active lanes of the 64-thread workgroup, column passes, problems per workgroup, LDS bytes, workgroups, columns; (problem
+ * i, column c) is lane (i % problems_per_wg) G + c % G of workgroup i / problems_per_wg in pass c / G.
+ * Errors, all found before the device is touched: ASSET_HIP_EINVAL (a null pointer, m < 1, ns < 1, a non-finite tf, the option errors
+ * of asset_hip_mesh_error_integrator), ASSET_HIP_ENOODE (no propagation kernels for this ODE), ASSET_HIP_ENODEV.  Nothing is written
+ * on an error. */
+int asset_hip_propagate(const char* ode, const double* y0, long long m, const double* tf, int ns, const asset_hip_integ_options* opt,
+                        double* xs, int* steps, int* status, int device);
+int asset_hip_propagate_stm(const char* ode, const double* y0, long long m, const double* tf, const asset_hip_integ_options* opt,
+                            double* xf, double* jac, int* steps, int* status, int device);
+int asset_hip_propagate_stm_lanes(const char* ode, const double* y0, long long m, const double* tf, const asset_hip_integ_options* opt,
+                                  double* xf, double* jac, int* steps, int* status, double* xf_last, int device);
+int asset_hip_propagate_plan(int xv, int uv, int pv, long long m, int stm, long long* out);
+
 /* ---- trajectory table: the transcription's own Hermite interpolant of a phase trajectory, on the device ----
  * Replaces LGLInterpTable for exact data (OptimalControl/LGLInterpTable.h:349-372, 480-669, 866-926), the table behind
  * ODEPhaseBase::refineTrajManual / updateMesh / returnTrajRange / returnTrajRangeND / returnTrajTable
