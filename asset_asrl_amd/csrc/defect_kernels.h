@@ -1158,9 +1158,13 @@ __device__ __forceinline__ void lgl_defect_body(const EvalArgs& a) {
         DIx[e * IRP + TF] = ditf + sb;
         DC[e * D::LDC + T] = dct - sd;
         DC[e * D::LDC + TF] = dctf + sd;
-        double fxv = h * sd;                             // defect value of row (i,r)  (LGLDefects.h:96-103)
+        // defect value of row (i,r)  (LGLDefects.h:96-103).  sum_j C_ij z_j first, h sd last: the C_ij sum to zero, so on a short
+        // segment the state terms cancel (Trapezoidal: z_0 - z_1, exact) and a small h sd added to z_0 first would be rounded at
+        // the size of z_0, not of the defect
+        double fxv = 0.0;
 #pragma unroll
         for (int jj = 0; jj < CS; jj++) fxv += (own ? tC[jj] : tab.C[i][jj]) * zv[jj];
+        fxv += h * sd;
         if constexpr (own) fx_hold = fxv;                // stored with the segment's other results (after the load fence)
         else if (a.FX) a.FX[seg * OR + e] = fxv;
       };
