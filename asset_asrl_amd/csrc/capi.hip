@@ -603,11 +603,21 @@ int asset_hip_kkt_layout(const char* ode, int mode, int blocked, int* nkkt, int*
 }
 
 // The launch plan (registry.h: plan_lgl) of one evaluation kind, with the default dispatch -- what a handle of `nseg` segments on
-// a device of `cus` compute units launches when no tuning knob is in effect
+// a device of `cus` compute units launches when no tuning knob is in effect.  `functions`: the handle of a plain function is
+// answered with its one launch (registry.h: plan_func); the query by name is for the transcriptions of an ODE only
 static int entry_launch_plan(const asset_hip::KernelEntry* ke, int what, int assembled, int nseg, int cus, bool res_record,
-                             asset_hip_launch_plan* out) {
+                             asset_hip_launch_plan* out, bool functions = false) {
   const int level = level_of(what);
   if (!out || level < 0 || (what & ~0xff) || (assembled && what < ASSET_HIP_JAC)) return fail(ASSET_HIP_EINVAL, "bad launch plan query");
+  if (ke->table->meta[asset_hip::MF_KIND] == 2 && functions) {   // a plain function: one launch (registry.h: plan_func)
+    if (nseg < 1) return fail(ASSET_HIP_EINVAL, "bad launch plan query (nseg and cus are positive)");
+    const asset_hip::FuncPlan f = asset_hip::plan_func(ke->table->meta, level, assembled != 0, nseg);
+    if (!ke->table->k[f.slot]) return fail(ASSET_HIP_ENOODE, std::string("the plan names a kernel this function lacks: ") + asset_hip::kslot_name(f.slot));
+    *out = asset_hip_launch_plan();
+    out->nsteps = 1;
+    out->step[0] = asset_hip_plan_step{f.slot, int(f.grid), 1, 64, (long long)f.lds_bytes, asset_hip::PLAN_NO_EXTRA, f.apw};
+    return 0;
+  }
   if (ke->table->meta[asset_hip::MF_KIND] != 1) return fail(ASSET_HIP_EINVAL, "launch plans are those of the transcriptions of an ODE");
   const bool adj = what == ASSET_HIP_CON_ADJGRAD || what == ASSET_HIP_JAC_ADJGRAD || what == ASSET_HIP_JAC_ADJGRAD_HESS;
   asset_hip::LaunchPlan p;
@@ -631,7 +641,7 @@ int asset_hip_launch_plan_query(const char* ode, int mode, int blocked, int what
 }
 int asset_hip_defect_launch_plan(asset_hip_defect_t h, int what, int assembled, asset_hip_launch_plan* out) {
   if (!h) return fail(ASSET_HIP_EINVAL, "null handle");
-  return entry_launch_plan(h->ke, what, assembled, h->nseg, h->cus, bool(h->lane[0]), out);
+  return entry_launch_plan(h->ke, what, assembled, h->nseg, h->cus, bool(h->lane[0]), out, true);
 }
 const char* asset_hip_kernel_slot_name(int slot) { return asset_hip::kslot_name(slot); }
 int asset_hip_kernel_slot_kinds(int slot) {
@@ -756,12 +766,10 @@ int asset_hip_bundle_eval_device(asset_hip_bundle_t b, int what, const double* d
     const int rc = fill_args(h, what, dX, dL ? dL[k] : nullptr, d_fx[k], d_agx ? d_agx[k] : nullptr, d_kkt ? d_kkt[k] : nullptr,
                              args.a[k]);
     if (rc) return rc;
-    const long long* m = h->ke->table->meta;
-    const bool staged = level >= 1 && m[asset_hip::MF_G] > 0;     // (as launch_func_table: the block kinds stage in LDS)
-    const int apw = staged ? int(m[asset_hip::MF_G]) : 64;
-    if (staged && size_t(m[asset_hip::MF_LDS_BYTES]) > shmem) shmem = size_t(m[asset_hip::MF_LDS_BYTES]);
+    const asset_hip::FuncPlan p = asset_hip::plan_func(h->ke->table->meta, level, false, h->nseg);   // (a bundle writes blocks only)
+    if (p.lds_bytes > shmem) shmem = p.lds_bytes;
     args.start[k] = blocks;
-    blocks += (h->nseg + apw - 1) / apw;
+    blocks += int(p.grid);
   }
   for (int k = n; k <= asset_hip::BUNDLE_MAX; k++) args.start[k] = blocks;
   void* kargs[] = {&args};

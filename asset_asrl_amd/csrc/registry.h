@@ -486,18 +486,29 @@ inline PlanRequest plan_request(int level, const EvalArgs& a) {
   return PlanRequest{level, a.KKT != nullptr, a.kmap != nullptr, a.AGX && a.L, a.lane_consts_res != nullptr};
 }
 
-// A plain function batched over applications: transcription id 0 (func_kernels.h)
+// A plain function batched over applications: transcription id 0 (func_kernels.h).  plan_func decides (no HIP call): the kernel
+// slot, the grid, the dynamic LDS and the applications per workgroup -- the block kinds of a function with FuncStage::APW > 0 take
+// APW applications per workgroup and stage their blocks in LDS, everything else takes 64 and no LDS.  The launcher, the bundle
+// launcher (capi.hip) and asset_hip_defect_launch_plan all read it.
+struct FuncPlan {
+  int slot;
+  unsigned grid;
+  size_t lds_bytes;
+  int apw;
+};
+inline FuncPlan plan_func(const long long* meta, int level, bool assembled, int nseg) {
+  const bool asmb = level >= 1 && assembled;
+  const bool staged = level >= 1 && !asmb && meta[MF_G] > 0;
+  const int apw = staged ? int(meta[MF_G]) : 64;
+  const int slot = level == 0 ? K_FUNC0 : (level == 1 ? (asmb ? K_FUNC1_ASM : K_FUNC1) : (asmb ? K_FUNC2_ASM : K_FUNC2));
+  return FuncPlan{slot, unsigned((nseg + apw - 1) / apw), staged ? size_t(meta[MF_LDS_BYTES]) : 0, apw};
+}
 inline hipError_t launch_func_table(const KernelTable& t, int level, const EvalArgs& a, hipStream_t st) {
   if (level < 0 || level > 2) return hipErrorInvalidValue;
   EvalArgs args = a;
   void* kargs[] = {&args};
-  const bool asmb = level >= 1 && a.kmap != nullptr;
-  // block kinds: APW applications per workgroup, their blocks staged in LDS (func_kernels.h: FuncStage)
-  const bool staged = level >= 1 && !asmb && t.meta[MF_G] > 0;
-  const int apw = staged ? int(t.meta[MF_G]) : 64;
-  const size_t shmem = staged ? size_t(t.meta[MF_LDS_BYTES]) : 0;
-  const int slot = level == 0 ? K_FUNC0 : (level == 1 ? (asmb ? K_FUNC1_ASM : K_FUNC1) : (asmb ? K_FUNC2_ASM : K_FUNC2));
-  return klaunch(t.k[slot], dim3((a.nseg + apw - 1) / apw), dim3(64), shmem, st, kargs);
+  const FuncPlan p = plan_func(t.meta, level, a.kmap != nullptr, a.nseg);
+  return klaunch(t.k[p.slot], dim3(p.grid), dim3(64), p.lds_bytes, st, kargs);
 }
 
 inline hipError_t entry_launch(const KernelEntry* ke, int level, const EvalArgs& a, int cus, hipStream_t st) {

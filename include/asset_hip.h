@@ -164,7 +164,10 @@ int asset_hip_kkt_layout(const char* ode, int mode, int blocked, int* nkkt, int*
  * LDS bytes and the kernel's second argument (0: none, 1: `group`, segments per workgroup row of a unit kernel, 2: the workspace
  * read-only); units_gp: EvalArgs::units_gp of the last launch (> 0: the dense part follows the XCD placement of the unit stage).
  * ASSET_HIP_ENOODE when the shape is unknown or lacks a kernel the plan names.  asset_hip_defect_launch_plan: the same for a
- * handle -- its own mesh, device and lane records -- so that run-time compiled shapes can be asked too.
+ * handle -- its own mesh, device and lane records -- so that run-time compiled shapes can be asked too.  The handle of a plain
+ * function (ASSET_HIP_FUNCTION) is answered with its one launch (csrc/registry.h: plan_func): slot K_FUNC0 / K_FUNC1 / K_FUNC2 /
+ * K_FUNC1_ASM / K_FUNC2_ASM, grid_x, block 64, the LDS bytes of the staged block kinds and group = applications per workgroup (64
+ * for the unstaged forms); the query by name stays with the transcriptions of an ODE.
  * asset_hip_kernel_slot_kinds: which kinds of run-time module name the slot (bit 0: transcription of an ODE, bit 1: plain
  * function, bit 2: bundle; see asset_hip_jit_compile). */
 typedef struct asset_hip_plan_step {

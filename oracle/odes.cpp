@@ -70,6 +70,7 @@ AD2_ODE(pathcon, 2, 3, 0)
 AD2_ODE(integrand_quad2, 1, 0, 0)
 AD2_ODE(pairprod, 1, 2, 0)
 AD2_ODE(integrand_powp, 1, 2, 0)
+AD2_ODE(integrand_wide7, 1, 5, 0)
 AD2_ODE(reentry_heating, 1, 1, 0)
 AD2_ODE(cartpole, 4, 1, 0)
 AD2_ODE(integrand_usq, 1, 0, 0)
@@ -134,6 +135,7 @@ GEN_DECL(pathcon)
 GEN_DECL(integrand_quad2)
 GEN_DECL(pairprod)
 GEN_DECL(integrand_powp)
+GEN_DECL(integrand_wide7)
 GEN_DECL(reentry_heating)
 GEN_DECL(cartpole)
 GEN_DECL(integrand_usq)
@@ -229,6 +231,7 @@ int oracle_get_ode4(const oracle_ode* ode, oracle_ode4* out) {
   TRY4(integrand_quad2)
   TRY4(pairprod)
   TRY4(integrand_powp)
+  TRY4(integrand_wide7)
   TRY4(reentry_heating)
   TRY4(cartpole)
   TRY4(integrand_usq)
@@ -280,6 +283,7 @@ int oracle_get_ode(const char* name, int provider, oracle_ode* out) {
   TRY(integrand_quad2, 1, 0, 0, nullptr)
   TRY(pairprod, 1, 2, 0, nullptr)
   TRY(integrand_powp, 1, 2, 0, nullptr)
+  TRY(integrand_wide7, 1, 5, 0, nullptr)
   TRY(reentry_heating, 1, 1, 0, nullptr)
   TRY(cartpole, 4, 1, 0, nullptr)
   TRY(integrand_usq, 1, 0, 0, nullptr)

@@ -356,6 +356,12 @@ template <class S>
 void integrand_powp(const S* y, S* f, const void*) {
   f[0] = y[3] * y[0] * y[0] + sin(y[1]) * y[2] + exp(-(y[0] * y[2])) / (1.0 + y[3] * y[3]);
 }
+// wide7: I(y0..y6) = y0 y1 sin(y2) + exp(-0.5 y3 y4) sqrt(1 + y5^2) + y6^2 y0 / (2 + y1^2) -- seven node values, every one coupled
+// with another: the node blocks of the quadrature's Hessian are dense (tests/golden/make_golden_func_entries.py); record (1, 5, 0)
+template <class S>
+void integrand_wide7(const S* y, S* f, const void*) {
+  f[0] = y[0] * y[1] * sin(y[2]) + exp(-0.5 * (y[3] * y[4])) * sqrt(1.0 + y[5] * y[5]) + y[6] * y[6] * y[0] / (2.0 + y[1] * y[1]);
+}
 
 // ------------------------------------------------------------------ shuttle reentry (5,2,0)
 template <class S>

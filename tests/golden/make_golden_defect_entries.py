@@ -426,10 +426,17 @@ def compute_segment(ode, mode, blocked, k):
     with _registered(ode):
         d = defect_value(ode, mode, blocked, [DE.var(mp.mpf(float(v)), i, IR) for i, v in enumerate(z)], ME)
     assert len(d) == OR
+    return blocks_of(d, z, lam)
+
+
+def blocks_of(d, z, lam):
+    """The fixture record of one application of a vector function: ``d`` = its outputs as DE over the inputs ``z``, contracted with
+    the multipliers ``lam`` by the same rules (lambda is exact)."""
+    IR, OR = z.size, lam.size
     il = np.tril_indices(IR)
     g, eg, ag = np.full(IR, _ZERO, dtype=object), np.zeros(IR), np.zeros(IR)
     h, eh, ah = np.full((IR, IR), _ZERO, dtype=object), np.zeros((IR, IR)), np.zeros((IR, IR))
-    for kk in range(OR):                                   # the lambda contraction, by the same rules (lambda is exact)
+    for kk in range(OR):
         l = mp.mpf(float(lam[kk]))
         al, exact = abs(float(lam[kk])), _pow2(float(lam[kk]))
         tg, th = d[kk].g * l, d[kk].h * l

@@ -7,7 +7,9 @@ Only the VALUE formulas of the reference are restated here --
     LGLIntegral         (t_{cs-1} - t_0) sum_i w_i I([x_i, p])                          LGLIntegrals.h:18-52
 -- evaluated in 50-digit mpmath arithmetic and differentiated exactly by the second-order forward AD of
 make_golden.py; the weights come from tests/golden/lgl_tables.json (the reference header, parsed).  The oracle's closed
-forms (oracle/pathfuncs.cpp) and the device are checked against tests/golden/pathfuncs.npz.
+forms (oracle/pathfuncs.cpp) and the host value of the product's definitions are checked against tests/golden/pathfuncs.npz
+(tests/test_pathfuncs_oracle.py).  The device is not: it is held entry by entry to the sibling fixture tests/golden/func_entries/
+(make_golden_func_entries.py, which imports the value formulas below; tests/test_gpu_func_entries.py).
 
 Usage:  python tests/golden/make_golden_pathfuncs.py
 """

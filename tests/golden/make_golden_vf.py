@@ -265,6 +265,16 @@ def asset_math_reference(seed: int = 950):
     return out
 
 
+def write_npz(path, data):
+    """An .npz of ``data`` that depends on nothing but its contents: members in sorted order, one fixed time stamp (np.savez stamps
+    the time of day on every member), deflate level 9.  ``path``: a file name or a binary file object."""
+    with zipfile.ZipFile(path, "w", zipfile.ZIP_DEFLATED, compresslevel=9) as z:
+        for key in sorted(data):
+            buf = io.BytesIO()
+            np.lib.format.write_array(buf, np.asarray(data[key]), allow_pickle=False)
+            z.writestr(zipfile.ZipInfo(key + ".npy", date_time=(1980, 1, 1, 0, 0, 0)), buf.getvalue(), zipfile.ZIP_DEFLATED, 9)
+
+
 def main():
     data = {}
     print(f"    {'case':<11} " + "    ".join(f"E_ref {k}" for k in vf_cases.ARRAYS))
@@ -275,11 +285,7 @@ def main():
             data[f"{name}_{key}"] = v
     data.update(asset_math_reference())
     path = os.path.join(HERE, "vf_ops.npz")
-    with zipfile.ZipFile(path, "w", zipfile.ZIP_DEFLATED, compresslevel=9) as z:      # (np.savez stamps the time of day on every member)
-        for key in sorted(data):
-            buf = io.BytesIO()
-            np.lib.format.write_array(buf, np.asarray(data[key]), allow_pickle=False)
-            z.writestr(zipfile.ZipInfo(key + ".npy", date_time=(1980, 1, 1, 0, 0, 0)), buf.getvalue(), zipfile.ZIP_DEFLATED, 9)
+    write_npz(path, data)
     print("wrote", os.path.basename(path), os.path.getsize(path), "bytes")
 
 

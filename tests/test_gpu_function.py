@@ -1,7 +1,9 @@
 """Plain vector functions batched over applications: a nonlinear path constraint written in
 the DSL, compiled at run time, against the oracle's AD2 derivatives of the same function pushed through the oracle's
 NLP restatement (blocks, scattered CSR values, RHS vectors); and the reference's LGL mesh-spacing relation against
-its closed-form Jacobian (MeshSpacingConstraints.h:128-142)."""
+its closed-form Jacobian (MeshSpacingConstraints.h:128-142).  The tolerance here is block-wise (1e-8 of a block's largest
+entry): index tables, assembly and known answers are what this file holds.  Entry-level accuracy of the same kernels, at every
+staging class of csrc/func_kernels.h: tests/test_gpu_func_entries.py."""
 import numpy as np
 import pytest
 

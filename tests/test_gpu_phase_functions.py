@@ -2,7 +2,9 @@
 (ODEPhaseBase.cpp:962-1061, 743-889, 1371-1375): the mesh-spacing equalities (LGLMeshSpacing over every defect,
 SingleMeshSpacing at every inner nodal state), the control-spline equalities of the spline control modes, integral
 objectives -- each one device evaluator, checked application by application against the oracle's restatements, and the
-row numbering / index tables against the registration order of the reference."""
+row numbering / index tables against the registration order of the reference.  The tolerance is block-wise (1e-8 of a block's
+largest entry); entry-level accuracy of these functions, and bundles against an independent reference:
+tests/test_gpu_func_entries.py."""
 import numpy as np
 import pytest
 

@@ -6,7 +6,8 @@
   header;
 * the product's weight tables (asset_asrl_amd/pathfuncs.py, synth.py) against that header, bit for bit;
 * the product's DSL definitions (host evaluation of the value) against the golden values.
-The device side is checked against the oracle in tests/test_gpu_function.py."""
+Nothing on the device is checked against this fixture: the device is held to the oracle in tests/test_gpu_function.py, and entry by
+entry at 50 digits to tests/golden/func_entries/ in tests/test_gpu_func_entries.py."""
 import json
 import os
 
