@@ -18,9 +18,11 @@
 
 #include "../../include/asset_hip.h"
 #include <dlfcn.h>
+#include <elf.h>
 #include <unistd.h>
 
 #include "registry.h"
+#include "propagate_event_kernels.h"
 #include "capi/kkt_map.h"
 #include "capi/owners.h"
 #include "capi/propagate_plan.h"
@@ -268,6 +270,48 @@ bool rtc_read(const std::string& path, RtcBlob& b) {
   return ok;
 }
 
+// The meta table of a module (rtc_device.h: asset_rtc_meta) read from the code object itself, on the host: the symbol's section and
+// offset in the ELF image.  Modules of kind 4 are registered this way, without a device (their launch loads them where it runs).
+bool rtc_meta_from_code(const std::vector<char>& code, long long* meta) {
+  static const char magic[4] = {0x7f, 'E', 'L', 'F'};
+  const auto it = std::search(code.begin(), code.end(), magic, magic + 4);   // (a bundled code object carries the image behind a header)
+  if (it == code.end()) return false;
+  const char* base = code.data() + (it - code.begin());
+  const size_t size = size_t(code.end() - it);
+  Elf64_Ehdr eh;
+  if (size < sizeof eh) return false;
+  std::memcpy(&eh, base, sizeof eh);
+  if (eh.e_ident[EI_CLASS] != ELFCLASS64 || eh.e_shentsize != sizeof(Elf64_Shdr) || eh.e_shoff > size ||
+      size_t(eh.e_shnum) * sizeof(Elf64_Shdr) > size - eh.e_shoff)
+    return false;
+  std::vector<Elf64_Shdr> sh(eh.e_shnum);
+  if (!sh.empty()) std::memcpy(sh.data(), base + eh.e_shoff, sh.size() * sizeof(Elf64_Shdr));
+  auto inside = [&](const Elf64_Shdr& h) { return h.sh_offset <= size && h.sh_size <= size - h.sh_offset; };
+  static const char want[] = "asset_rtc_meta";
+  const size_t bytes = sizeof(long long) * asset_hip::MF_COUNT;
+  for (const Elf64_Shdr& st : sh) {
+    if ((st.sh_type != SHT_SYMTAB && st.sh_type != SHT_DYNSYM) || st.sh_entsize != sizeof(Elf64_Sym) || !inside(st) || st.sh_link >= sh.size())
+      continue;
+    const Elf64_Shdr& str = sh[st.sh_link];
+    if (!inside(str)) continue;
+    for (size_t k = 0; k < st.sh_size / sizeof(Elf64_Sym); k++) {
+      Elf64_Sym sym;
+      std::memcpy(&sym, base + st.sh_offset + k * sizeof sym, sizeof sym);
+      if (sym.st_name >= str.sh_size || str.sh_size - sym.st_name < sizeof want ||
+          std::memcmp(base + str.sh_offset + sym.st_name, want, sizeof want) != 0)
+        continue;
+      if (sym.st_shndx >= sh.size() || sym.st_size != bytes) return false;
+      const Elf64_Shdr& sec = sh[sym.st_shndx];
+      if (sec.sh_type == SHT_NOBITS || !inside(sec) || sym.st_value < sec.sh_addr || sym.st_value - sec.sh_addr > sec.sh_size ||
+          sec.sh_size - (sym.st_value - sec.sh_addr) < bytes)
+        return false;
+      std::memcpy(meta, base + sec.sh_offset + (sym.st_value - sec.sh_addr), bytes);
+      return true;
+    }
+  }
+  return false;
+}
+
 int rtc_compile(const char* source, const char* functor, int kind, int mode, int blocked, int seg_per_group,
                 const char* const* options, int noptions, RtcBlob& out) {
   hiprtcProgram prog = nullptr;
@@ -317,7 +361,7 @@ int rtc_compile(const char* source, const char* functor, int kind, int mode, int
 
 int asset_hip_jit_compile(const char* source, const char* functor, int kind, int mode, int blocked, int seg_per_group,
                           const char* const* options, int noptions, const char* cache_path) {
-  if (!source || !functor || !cache_path || kind < 1 || kind > 3) return fail(ASSET_HIP_EINVAL, "bad jit arguments");
+  if (!source || !functor || !cache_path || kind < 1 || kind > 4) return fail(ASSET_HIP_EINVAL, "bad jit arguments");
   RtcBlob blob;
   const int rc = rtc_compile(source, functor, kind, mode, blocked, seg_per_group, options, noptions, blob);
   if (rc) return rc;
@@ -327,7 +371,7 @@ int asset_hip_jit_compile(const char* source, const char* functor, int kind, int
 
 int asset_hip_jit_plugin(const char* name, const char* source, const char* functor, int kind, int mode, int blocked,
                          int seg_per_group, const char* const* options, int noptions, const char* cache_path) {
-  if (!name || !functor || kind < 1 || kind > 3) return fail(ASSET_HIP_EINVAL, "bad jit arguments");
+  if (!name || !functor || kind < 1 || kind > 4) return fail(ASSET_HIP_EINVAL, "bad jit arguments");
   if (find_entry(name, kind >= 2 ? ASSET_HIP_FUNCTION : mode, kind >= 2 ? 0 : blocked)) return 0;
   RtcBlob blob;
   if (!(cache_path && rtc_read(cache_path, blob))) {
@@ -344,17 +388,24 @@ int asset_hip_jit_plugin(const char* name, const char* source, const char* funct
   std::unique_ptr<asset_hip::RtcModule> rtc(new asset_hip::RtcModule());
   rtc->code.swap(blob.code);
   rtc->names.swap(blob.names);
-  hipModule_t mod = nullptr;
-  hipError_t e = rtc->module_on_current_device(&mod);
-  if (e != hipSuccess) return hipfail(e, "loading the run-time module (hipModuleLoadData / hipModuleGetFunction)");
   std::unique_ptr<asset_hip::KernelTable> table(new asset_hip::KernelTable());
-  hipDeviceptr_t dmeta = nullptr;
-  size_t mbytes = 0;
-  e = hipModuleGetGlobal(&dmeta, &mbytes, mod, "asset_rtc_meta");
-  if (e != hipSuccess || mbytes != sizeof table->meta)
-    return fail(ASSET_HIP_ECOMPILE, "the module has no asset_rtc_meta table of the expected size (rtc_device.h)");
-  if ((e = hipMemcpy(table->meta, reinterpret_cast<void*>(dmeta), sizeof table->meta, hipMemcpyDeviceToHost)) != hipSuccess)
-    return hipfail(e, "reading asset_rtc_meta");
+  if (kind == 4) {
+    // an ODE with event functions: the table comes from the code object on the host, so that asset_hip_propagate_events can check
+    // its arguments against it before a device is touched; the module is loaded by its first launch
+    if (!rtc_meta_from_code(rtc->code, table->meta))
+      return fail(ASSET_HIP_ECOMPILE, "the module has no asset_rtc_meta table of the expected size (rtc_device.h)");
+  } else {
+    hipModule_t mod = nullptr;
+    hipError_t e = rtc->module_on_current_device(&mod);
+    if (e != hipSuccess) return hipfail(e, "loading the run-time module (hipModuleLoadData / hipModuleGetFunction)");
+    hipDeviceptr_t dmeta = nullptr;
+    size_t mbytes = 0;
+    e = hipModuleGetGlobal(&dmeta, &mbytes, mod, "asset_rtc_meta");
+    if (e != hipSuccess || mbytes != sizeof table->meta)
+      return fail(ASSET_HIP_ECOMPILE, "the module has no asset_rtc_meta table of the expected size (rtc_device.h)");
+    if ((e = hipMemcpy(table->meta, reinterpret_cast<void*>(dmeta), sizeof table->meta, hipMemcpyDeviceToHost)) != hipSuccess)
+      return hipfail(e, "reading asset_rtc_meta");
+  }
   if (table->meta[asset_hip::MF_KIND] != kind || (kind == 1 && (table->meta[asset_hip::MF_MODE] != mode ||
                                                                table->meta[asset_hip::MF_BLOCKED] != (blocked ? 1 : 0))))
     return fail(ASSET_HIP_EINVAL, "the module was compiled for another transcription / kind than requested");
@@ -368,6 +419,19 @@ int asset_hip_jit_plugin(const char* name, const char* source, const char* funct
   ke->next = asset_hip::registry_head();
   asset_hip::registry_head() = ke;
   return 0;
+}
+
+// The meta table of a cached module file, read on the host as asset_hip_jit_plugin reads it for kind 4 (rtc_meta_from_code): for
+// tools and tests -- a file that is cut short or damaged is an error, never a crash.  Returns MF_COUNT.
+int asset_hip_rtc_module_meta(const char* cache_path, long long* meta, int cap) {
+  if (!cache_path || !meta) return fail(ASSET_HIP_EINVAL, "null argument");
+  if (cap < asset_hip::MF_COUNT) return fail(ASSET_HIP_EINVAL, "output buffer too small");
+  RtcBlob blob;
+  if (!rtc_read(cache_path, blob)) return fail(ASSET_HIP_EINVAL, std::string("no compiled module at ") + cache_path);
+  long long tmp[asset_hip::MF_COUNT];
+  if (!rtc_meta_from_code(blob.code, tmp)) return fail(ASSET_HIP_EINVAL, "the code object holds no readable asset_rtc_meta table");
+  for (int k = 0; k < asset_hip::MF_COUNT; k++) meta[k] = tmp[k];
+  return asset_hip::MF_COUNT;
 }
 
 int asset_hip_load_plugin(const char* path) {
@@ -517,6 +581,8 @@ int asset_hip_defect_create(const asset_hip_defect_desc* d, asset_hip_defect_t* 
     return fail(ASSET_HIP_ENOODE, buf);
   }
   if (ke->table->meta[asset_hip::MF_KIND] == 3) return fail(ASSET_HIP_EINVAL, "a bundle is launched through asset_hip_bundle_*, it is not a function");
+  if (ke->table->meta[asset_hip::MF_KIND] == 4)
+    return fail(ASSET_HIP_EINVAL, "an event module is launched through asset_hip_propagate_events, it is not a function");
   // (before anything is allocated: the commonest set-up error)
   if (const int rc = check_index_tables(ke, d->nseg, d->vindex, d->cindex, d->n_primal, d->n_equal)) return rc;
   if (const int rc = use_device(d->device, "no HIP device visible: the evaluator has no CPU fallback")) return rc;
@@ -598,6 +664,8 @@ int asset_hip_defect_kkt_layout(asset_hip_defect_t h, int* stride, int32_t* rows
 int asset_hip_kkt_layout(const char* ode, int mode, int blocked, int* nkkt, int* stride, int32_t* rows, int32_t* cols) {
   const asset_hip::KernelEntry* ke = ode ? find_entry(ode, mode, blocked) : nullptr;
   if (!ke) return fail(ASSET_HIP_ENOODE, "no device code compiled for this (ode, mode, blocked)");
+  if (ke->table->meta[asset_hip::MF_KIND] == 4)
+    return fail(ASSET_HIP_EINVAL, "an event module is launched through asset_hip_propagate_events, it is not a function");
   if (nkkt) *nkkt = ke->nkkt;
   return entry_kkt_layout(ke, stride, rows, cols);
 }
@@ -637,6 +705,8 @@ int asset_hip_launch_plan_query(const char* ode, int mode, int blocked, int what
                                 asset_hip_launch_plan* out) {
   const asset_hip::KernelEntry* ke = ode ? find_entry(ode, mode, blocked) : nullptr;
   if (!ke) return fail(ASSET_HIP_ENOODE, "no device code compiled for this (ode, mode, blocked)");
+  if (ke->table->meta[asset_hip::MF_KIND] == 4)
+    return fail(ASSET_HIP_EINVAL, "an event module is launched through asset_hip_propagate_events, it is not a function");
   return entry_launch_plan(ke, what, assembled, nseg, cus, asset_hip::entry_lane_bytes(ke, 0) > 0, out);
 }
 int asset_hip_defect_launch_plan(asset_hip_defect_t h, int what, int assembled, asset_hip_launch_plan* out) {
@@ -646,7 +716,7 @@ int asset_hip_defect_launch_plan(asset_hip_defect_t h, int what, int assembled, 
 const char* asset_hip_kernel_slot_name(int slot) { return asset_hip::kslot_name(slot); }
 int asset_hip_kernel_slot_kinds(int slot) {
   int kinds = 0;
-  for (int kind = 1; kind <= 3; kind++)
+  for (int kind = 1; kind <= 4; kind++)
     if (!asset_hip::rtc_kernel_expr(slot, kind, "F", ASSET_HIP_LGL3, false, 1).empty()) kinds |= 1 << (kind - 1);
   return kinds;
 }
@@ -978,6 +1048,12 @@ const asset_hip::KernelEntry* prop_entry(const char* ode) {
   return (ke && asset_hip::prop_home(ke->mode, ke->blocked != 0) && ke->table->meta[asset_hip::MF_KIND] == 1 && asset_hip::entry_has_prop(ke)) ? ke : nullptr;
 }
 
+// an ODE with event functions: a run-time module of kind 4 (asset_hip_jit_plugin), registered under its own name
+const asset_hip::KernelEntry* event_entry(const char* module) {
+  const asset_hip::KernelEntry* ke = find_entry(module, ASSET_HIP_FUNCTION, 0);
+  return (ke && ke->table->meta[asset_hip::MF_KIND] == 4 && ke->table->k[asset_hip::K_PROP_EVENT]) ? ke : nullptr;
+}
+
 // the option rules of asset_hip_mesh_error_integrator
 int integ_options_checked(const asset_hip_integ_options* opt, asset_hip::IntegOptions& o) {
   o = asset_hip::IntegOptions{0.01, 0.01 / 10000, 0.01 * 10000, 3.0, 1, 100000};
@@ -1064,6 +1140,96 @@ int asset_hip_propagate_stm_lanes(const char* ode, const double* y0, long long m
   if (!xf_last) return fail(ASSET_HIP_EINVAL, "null argument");
   return propagate_impl(ode, y0, m, tf, 1, opt, true, xf, jac, steps, status, xf_last, device);
 }
+int asset_hip_event_module_sizes(const char* module, int* xv, int* uv, int* pv, int* ne) {
+  if (!module) return fail(ASSET_HIP_EINVAL, "null argument");
+  const asset_hip::KernelEntry* ke = event_entry(module);
+  if (!ke) return fail(ASSET_HIP_ENOODE, std::string("no event module registered as '") + module + "'");
+  if (xv) *xv = ke->xv;
+  if (uv) *uv = ke->uv;
+  if (pv) *pv = ke->pv;
+  if (ne) *ne = ke->orr;
+  return 0;
+}
+
+int asset_hip_propagate_events(const char* module, const double* y0, long long m, const double* tf, const asset_hip_integ_options* opt,
+                               int ne, const int* direction, const int* stop, double event_tol, int max_event_iters, int max_locs,
+                               double* xf, double* t_end, int* stopped, int* ev_count, double* ev_rows, double* ev_resid, int* ev_conv,
+                               int* steps, int* status, int device) {
+  if (!module || !y0 || !tf || !direction || !stop || !xf || !t_end || !stopped || !ev_count || !ev_rows || !ev_resid || !ev_conv)
+    return fail(ASSET_HIP_EINVAL, "null argument");
+  if (m < 1) return fail(ASSET_HIP_EINVAL, "m must be at least 1");
+  const asset_hip::KernelEntry* ke = event_entry(module);
+  if (!ke) return fail(ASSET_HIP_ENOODE, std::string("no event module registered as '") + module + "' (asset_hip_jit_plugin, kind 4)");
+  if (ne != ke->orr) return fail(ASSET_HIP_EINVAL, "ne is " + std::to_string(ne) + " but the module has " + std::to_string(ke->orr) + " events");
+  if (!(event_tol > 0.0)) return fail(ASSET_HIP_EINVAL, "event_tol must be positive");
+  if (max_event_iters < 1) return fail(ASSET_HIP_EINVAL, "max_event_iters must be at least 1");
+  if (max_locs < 1) return fail(ASSET_HIP_EINVAL, "max_locs must be at least 1");
+  for (int j = 0; j < ne; j++) {
+    if (direction[j] < -1 || direction[j] > 1) return fail(ASSET_HIP_EINVAL, "direction must be -1, 0 or 1 (event " + std::to_string(j) + ")");
+    if (stop[j] < 0) return fail(ASSET_HIP_EINVAL, "stop must not be negative (event " + std::to_string(j) + ")");
+    if (stop[j] > max_locs)
+      return fail(ASSET_HIP_EINVAL, "stop exceeds max_locs: the stopping occurrence would not be located (event " + std::to_string(j) + ")");
+  }
+  asset_hip::IntegOptions o;
+  if (const int rc = integ_options_checked(opt, o)) return rc;
+  for (long long i = 0; i < m; i++)
+    if (!std::isfinite(tf[i])) return fail(ASSET_HIP_EINVAL, "tf is not finite (problem " + std::to_string(i) + ")");
+  const int n = ke->xv, N = ke->xv + 1 + ke->uv + ke->pv;
+  const asset_hip::PropPlan plan = asset_hip::propagate_plan(ke->xv, ke->uv, ke->pv, m, 0);
+  if (plan.grid < 1 || plan.grid > 0x7fffffffLL || size_t(plan.lds_bytes) > 64 * 1024)
+    return fail(ASSET_HIP_EINVAL, "the batch does not fit one launch (workgroups or LDS)");
+  if (const int rc = use_device(device, "no HIP device visible: the propagation has no CPU fallback")) return rc;
+  // one allocation of doubles: y0 | tf | abs | rel | xf | t_end | ev_rows | ev_resid; one of ints: steps | status | stopped | ev_count | ev_conv
+  const size_t um = size_t(m), sz_y = um * N, sz_x = um * n, sz_e = um * ne * size_t(max_locs), sz_r = sz_e * (n + 1), sz_c = um * ne;
+  DeviceBuffer<double> buf;
+  DeviceBuffer<int> ibuf;
+  HIP_TRY(buf.allocate(sz_y + um + 2 * size_t(n) + sz_x + um + sz_r + sz_e));
+  HIP_TRY(ibuf.allocate(um * 4 + sz_c + sz_e));
+  asset_hip::PropEventArgs a;
+  a.m = m, a.lanes = plan.lanes, a.max_iters = max_event_iters, a.max_locs = max_locs, a.event_tol = event_tol, a.opt = o;
+  for (int j = 0; j < asset_hip::PROP_EVENT_MAX; j++) a.direction[j] = j < ne ? direction[j] : 0, a.stop[j] = j < ne ? stop[j] : 0;
+  double* p = buf.get();
+  double* d_y = p;
+  a.y0 = p, p += sz_y;
+  double* d_tf = p;
+  a.tf = p, p += um;
+  double* d_tols = p;
+  a.abs_tols = p, p += n;
+  a.rel_tols = p, p += n;
+  a.xf = p, p += sz_x;
+  a.t_end = p, p += um;
+  a.ev_rows = p, p += sz_r;
+  a.ev_resid = p;
+  int* q = ibuf.get();
+  a.steps = q, q += um * 2;
+  a.status = q, q += um;
+  a.stopped = q, q += um;
+  a.ev_count = q, q += sz_c;
+  a.ev_conv = q;
+  std::vector<double> tols(2 * size_t(n));
+  for (int k = 0; k < n; k++) {
+    tols[k] = (opt && opt->abs_tols) ? opt->abs_tols[k] : 1.0e-12;
+    tols[n + k] = (opt && opt->rel_tols) ? opt->rel_tols[k] : 0.0;
+  }
+  HIP_TRY_AS(hipMemcpy(d_y, y0, sz_y * sizeof(double), hipMemcpyHostToDevice), "hipMemcpy(y0)");
+  HIP_TRY_AS(hipMemcpy(d_tf, tf, um * sizeof(double), hipMemcpyHostToDevice), "hipMemcpy(tf)");
+  HIP_TRY_AS(hipMemcpy(d_tols, tols.data(), tols.size() * sizeof(double), hipMemcpyHostToDevice), "hipMemcpy(tolerances)");
+  void* kargs[] = {&a};
+  HIP_TRY_AS(asset_hip::klaunch(ke->table->k[asset_hip::K_PROP_EVENT], dim3(unsigned(plan.grid)), dim3(64), size_t(plan.lds_bytes), nullptr,
+                                kargs), "event propagation kernel");
+  HIP_TRY_AS(hipDeviceSynchronize(), "event propagation kernel");
+  HIP_TRY_AS(hipMemcpy(xf, a.xf, sz_x * sizeof(double), hipMemcpyDeviceToHost), "hipMemcpy(states)");
+  HIP_TRY_AS(hipMemcpy(t_end, a.t_end, um * sizeof(double), hipMemcpyDeviceToHost), "hipMemcpy(t_end)");
+  HIP_TRY_AS(hipMemcpy(ev_rows, a.ev_rows, sz_r * sizeof(double), hipMemcpyDeviceToHost), "hipMemcpy(ev_rows)");
+  HIP_TRY_AS(hipMemcpy(ev_resid, a.ev_resid, sz_e * sizeof(double), hipMemcpyDeviceToHost), "hipMemcpy(ev_resid)");
+  HIP_TRY_AS(hipMemcpy(stopped, a.stopped, um * sizeof(int), hipMemcpyDeviceToHost), "hipMemcpy(stopped)");
+  HIP_TRY_AS(hipMemcpy(ev_count, a.ev_count, sz_c * sizeof(int), hipMemcpyDeviceToHost), "hipMemcpy(ev_count)");
+  HIP_TRY_AS(hipMemcpy(ev_conv, a.ev_conv, sz_e * sizeof(int), hipMemcpyDeviceToHost), "hipMemcpy(ev_conv)");
+  if (steps) HIP_TRY_AS(hipMemcpy(steps, a.steps, um * 2 * sizeof(int), hipMemcpyDeviceToHost), "hipMemcpy(steps)");
+  if (status) HIP_TRY_AS(hipMemcpy(status, a.status, um * sizeof(int), hipMemcpyDeviceToHost), "hipMemcpy(status)");
+  return 0;
+}
+
 int asset_hip_propagate_plan(int xv, int uv, int pv, long long m, int stm, long long* out) {
   if (!out) return fail(ASSET_HIP_EINVAL, "null argument");
   const asset_hip::PropPlan p = asset_hip::propagate_plan(xv, uv, pv, m, stm);

@@ -15,7 +15,7 @@
 namespace asset_hip {
 
 enum MetaField {
-  MF_KIND = 0,       // 1: transcription of an ODE, 2: plain function
+  MF_KIND = 0,       // 1: transcription of an ODE, 2: plain function, 3: bundle of plain functions, 4: an ODE with event functions
   MF_XV, MF_UV, MF_PV,
   MF_MODE,           // ASSET_HIP_* transcription id (0 for plain functions)
   MF_BLOCKED,
@@ -89,6 +89,14 @@ struct BundleMeta {
   static_assert(MF_BYTES_ODE + BUNDLE_MAX <= MF_COUNT, "signature words fit the table");
   static constexpr long long v[MF_COUNT] = {3, sizeof...(Fs), 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0,
                                             (long long)(FuncDims<Fs>::IR) * 65536 + FuncDims<Fs>::OR...};
+};
+
+// An ODE with its event functions (propagate_event_kernels.h: prop_event_kernel<Ode, Ev>): MF_KIND 4, the ODE's sizes, MF_IR = its
+// input count and MF_OR = the number of events.  The host reads the table from the code object itself (capi.hip), so that the
+// arguments of a propagation with events are checked before a device is touched.
+template <class Ode, class Ev>
+struct EventMeta {
+  static constexpr long long v[MF_COUNT] = {4, Ode::XV, Ode::UV, Ode::PV, 0, 0, Ode::NIN, Ev::XV};
 };
 
 }  // namespace asset_hip

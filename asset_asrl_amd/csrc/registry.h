@@ -116,7 +116,8 @@ inline hipError_t klaunch(const KRef& k, dim3 grid, dim3 block, size_t shmem, hi
 // X(slot, family, condition, kernel template, trailing template arguments...).  The family says what precedes the trailing
 // arguments -- LGLG: <Ode, SCH, BLOCKED, G, ...>, LGL: <Ode, SCH, BLOCKED, ...>, NONE: <...> (all three: transcriptions of an ODE),
 // ODE: <Ode, ...> (kernels of the ODE alone, whatever the transcription: they live in ONE entry per ODE, prop_home below),
-// FUNC: <F, ...> (plain functions), BUNDLE: <..., Fs...> (bundles, run-time modules only) -- and the condition is the compile-time
+// FUNC: <F, ...> (plain functions), BUNDLE: <..., Fs...> (bundles, run-time modules only), ODEEV: <Ode, Ev, ...> (an ODE with an event
+// functor, run-time modules only: rtc_device.h, ASSET_RTC_PROP_EVENTS) -- and the condition is the compile-time
 // one (D = Dims<Ode, SCH, BLOCKED>) under which a shape linked into the library has the kernel.  The slot enum, the static tables
 // (lgl_static_table, func_static_table) and the name expressions of a run-time module (rtc_kernel_expr, which names every slot of
 // its kind: rtc_device.h compiles the variants a shape lacks to empty kernels) are all generated from this list.
@@ -195,7 +196,9 @@ constexpr bool prop_home(int sch, bool blocked) { return sch == PROP_HOME_MODE &
   /* batched propagation (propagate_kernels.h): end states and samples, state + STM columns, the STM's assembly */               \
   X(K_PROP_BATCH, ODE, prop_home(SCH, BLOCKED), prop_batch_kernel)                                                              \
   X(K_PROP_STM, ODE, prop_home(SCH, BLOCKED), prop_stm_kernel)                                                                  \
-  X(K_PROP_JAC, ODE, prop_home(SCH, BLOCKED), prop_stm_jac_kernel)
+  X(K_PROP_JAC, ODE, prop_home(SCH, BLOCKED), prop_stm_jac_kernel)                                                               \
+  /* propagation with events (propagate_event_kernels.h): the ODE's functor and the event functor in one run-time module */      \
+  X(K_PROP_EVENT, ODEEV, true, prop_event_kernel)
 
 #define ASSET_X_ENUM(NAME, ...) NAME,
 enum KSlot : int { ASSET_KERNELS(ASSET_X_ENUM) K_COUNT };
@@ -597,6 +600,7 @@ inline hipError_t entry_lane_setup(const KernelEntry* ke, int level, void* out, 
 #define ASSET_FILL_ODE(NAME, COND, T, ...) if constexpr (COND) r.k[NAME].host = ASSET_KPTR(T<Ode, ##__VA_ARGS__>);
 #define ASSET_FILL_FUNC(NAME, COND, T, ...)
 #define ASSET_FILL_BUNDLE(NAME, COND, T, ...)
+#define ASSET_FILL_ODEEV(NAME, COND, T, ...)
 #define ASSET_X_FILL(NAME, FAMILY, COND, T, ...) ASSET_FILL_##FAMILY(NAME, COND, T, ##__VA_ARGS__)
 template <class Ode, int SCH, bool BLOCKED, int G>
 const KernelTable* lgl_static_table() {
@@ -635,6 +639,7 @@ const KernelTable* func_static_table() {
 #undef ASSET_FILL_ODE
 #undef ASSET_FILL_FUNC
 #undef ASSET_FILL_BUNDLE
+#undef ASSET_FILL_ODEEV
 #undef ASSET_X_FILL
 #undef ASSET_KPTR
 
@@ -657,7 +662,8 @@ struct StaticEntry {   // (static initialisation: the table is filled and the en
   static ::asset_hip::StaticEntry entry_##ODE##_##CSV##_##BLK(ODE::name(), ::asset_hip::lgl_static_table<ODE, CSV, (BLK != 0), G>());
 
 // ---- name expressions of the kernels of a run-time module (capi.hip: asset_hip_jit_plugin) -----------------------------
-// kind 1: `type` is the ODE functor, kind 2: the function functor, kind 3: the comma-separated functor list of a bundle.  Slots
+// kind 1: `type` is the ODE functor, kind 2: the function functor, kind 3: the comma-separated functor list of a bundle, kind 4: "Ode, Ev",
+// the ODE functor and the event functor of a propagation with events.  Slots
 // without a kernel for that kind: empty string.
 inline std::string rtc_kernel_expr(int slot, int kind, const std::string& type, int csv, bool blocked, int g) {
   const std::string none, lgl = type + ", " + std::to_string(csv) + ", " + (blocked ? "true" : "false"), lglg = lgl + ", " + std::to_string(g);
@@ -673,6 +679,7 @@ inline std::string rtc_kernel_expr(int slot, int kind, const std::string& type, 
 #define ASSET_RTC_ODE (prop_home(csv, blocked) ? 1 : 0), type
 #define ASSET_RTC_FUNC 2, type
 #define ASSET_RTC_BUNDLE 3, type, true
+#define ASSET_RTC_ODEEV 4, type
 #define ASSET_X_EXPR(NAME, FAMILY, COND, T, ...) case NAME: return expr(#T, #__VA_ARGS__, ASSET_RTC_##FAMILY);
   switch (slot) { ASSET_KERNELS(ASSET_X_EXPR) }
 #undef ASSET_X_EXPR
@@ -682,6 +689,7 @@ inline std::string rtc_kernel_expr(int slot, int kind, const std::string& type, 
 #undef ASSET_RTC_ODE
 #undef ASSET_RTC_FUNC
 #undef ASSET_RTC_BUNDLE
+#undef ASSET_RTC_ODEEV
   return "";
 }
 

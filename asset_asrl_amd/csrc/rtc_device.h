@@ -3,6 +3,7 @@
 //     #include "ode.h"                      the generated functor
 //     #include "<csrc>/rtc_device.h"
 //     ASSET_RTC_LGL(OdeName, CSV, BLK, G)   or   ASSET_RTC_FUNC(FnName)   or   ASSET_RTC_BUNDLE(Fn0, Fn1, ...)
+//     or   ASSET_RTC_PROP_EVENTS(OdeName, EvName)   (both functors in the one source: propagate_event_kernels.h)
 // and the loader names the kernels it wants (hiprtcAddNameExpression): every variant the launcher of registry.h may use.
 // Variants a shape does not have compile to empty kernels (lgl_variant_valid, the guards of the wide / units / setup
 // kernels), so the list does not depend on the shape.
@@ -12,6 +13,7 @@
 #include "interp_kernels.h"
 #include "mesh_kernels.h"
 #include "propagate_kernels.h"
+#include "propagate_event_kernels.h"
 
 #define ASSET_RTC_LGL(ODE, CSV, BLK, G)                                                                            \
   extern "C" __device__ const long long asset_rtc_meta[::asset_hip::MF_COUNT] = {                                  \
@@ -22,6 +24,9 @@
 #define ASSET_RTC_BUNDLE(...)                                                                                      \
   extern "C" __device__ const long long asset_rtc_meta[::asset_hip::MF_COUNT] = {                                  \
       ASSET_RTC_META_LIST((::asset_hip::BundleMeta<__VA_ARGS__>::v))};
+#define ASSET_RTC_PROP_EVENTS(ODE, EV)                                                                             \
+  extern "C" __device__ const long long asset_rtc_meta[::asset_hip::MF_COUNT] = {                                  \
+      ASSET_RTC_META_LIST((::asset_hip::EventMeta<ODE, EV>::v))};
 // (an array cannot be initialised from another array: spell the elements out)
 #define ASSET_RTC_META_LIST(V)                                                                                     \
   V[0], V[1], V[2], V[3], V[4], V[5], V[6], V[7], V[8], V[9], V[10], V[11], V[12], V[13], V[14], V[15], V[16], V[17],  \

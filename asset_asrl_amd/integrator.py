@@ -1,5 +1,5 @@
-"""``ode.integrator(...)``: batched propagation of an ODE on the device (csrc/propagate_kernels.h; include/asset_hip.h:
-asset_hip_propagate, asset_hip_propagate_stm).
+"""``ode.integrator(...)``: batched propagation of an ODE on the device (csrc/propagate_kernels.h, csrc/propagate_event_kernels.h;
+include/asset_hip.h: asset_hip_propagate, asset_hip_propagate_stm, asset_hip_propagate_events).
 
 The reference's ``Integrator`` (Integrators/Integrator.h) in its own method names and return shapes, for the integrator WITHOUT a
 controller: rows go in and come out as full ``[x, t, u, p]`` rows, and the controls and parameters of a row are held for the whole
@@ -20,7 +20,22 @@ State-transition matrix: ``J`` has the reference's layout ``[XV, XV + 1 + UV + P
 held fixed (what the reference chains step by step, Integrator.h:1317-1349); the two time columns are the flow's,
 ``-S_x f(x0, t0, u, p)`` and ``f(xf, tf, u, p)``.
 
-Out of scope: events; ``integrate_stm2`` (second derivatives); controllers other than held controls (a trajectory's control table);
+Events (Integrator.h:536-730, 1047-1159): ``integrate(x0, tf, events)`` and ``integrate_parallel(x0s, tfs, events)`` take a list of
+``(g, direction, stop)`` -- ``g`` a scalar ``vf`` function of the ODE's input row ``[x, t, u, p]``, ``direction`` -1, 0 or +1, ``stop`` 0
+(never) or k (stop at the k-th occurrence) -- and return ``(row, eventlocs)`` per problem: ``eventlocs[j]`` lists the full rows at
+which event j occurred.  After every accepted step event j occurred iff ``g(prev) g(next) < 0`` and the sign of ``g(next)`` matches
+a non-zero direction (a value that is exactly zero at a step end never counts); a propagation that stops ends at the END of the
+accepted step in which an event reached its stop count, and the end row's time is that time.  Where the reference root-finds on
+the interpolant of its step table, an occurrence is located here on the integrator itself: the state is the result of ONE step of
+size ``theta h`` from the start of the bracketing step, the root in ``theta`` found by Illinois regula falsi within ``MaxEventIters``
+evaluations, done when ``|g| < EventTol`` or the bracket's half-width in time is ``< EventTol`` (the reference's defaults, 1e-6 and 10).
+An occurrence that is not located within them is dropped from ``eventlocs``, as the reference gives up silently; ``details=True``
+shows it.  ``MaxEventLocs`` (8) occurrences per problem and event are located and stored; later ones are counted (``ev_count``) and
+count towards ``stop``.  The event functions are compiled with the ODE into one module per (ODE, event functions) at first use.
+Locating does not disturb the propagation: the end state and step counts of a problem whose events never stop it are those of the
+call without events, bit for bit.
+
+Out of scope: dense output with events and the STM with events (``NotImplementedError``); ``integrate_stm2`` (second derivatives); controllers other than held controls (a trajectory's control table);
 DOPRI54; ``calc_global_error`` (one serial propagation, not a batch).  ``Phase.AutoScaling`` does not enter: this is an ODE-level
 feature and works in the ODE's own units.
 """
@@ -67,6 +82,8 @@ class Integrator(IntegratorOptions):
         self.ode, self.device = ode, int(device)
         self._uv, self._pv = ode.UVars(), ode.PVars()
         self._name = None
+        self.EventTol, self.MaxEventIters, self.MaxEventLocs = 1.0e-6, 10, 8      # Integrator.h:304-305; stored occurrences per event
+        self._event_modules = {}
 
     # ---- plumbing
     def _width(self):
@@ -120,29 +137,140 @@ class Integrator(IntegratorOptions):
             out[:, -1, n] = T
         return out
 
+    # ---- events
+    def _events(self, events):
+        """(functions, direction[ne], stop[ne]) of a list of ``(g, direction, stop)``."""
+        ev = [tuple(e) for e in events]
+        if not 1 <= len(ev) <= 8:
+            raise ValueError("1..8 events")
+        if any(len(e) != 3 for e in ev):
+            raise ValueError("an event is (g, direction, stop)")
+        funcs = [e[0] for e in ev]
+        for j, g in enumerate(funcs):
+            if g.IRows() != self._width():
+                raise ValueError(f"event {j} has {g.IRows()} inputs, the ODE's rows have {self._width()}")
+            if g.ORows() != 1:
+                raise ValueError(f"event {j} is not a scalar function")
+        direction = np.array([int(e[1]) for e in ev], dtype=np.int32)
+        stop = np.array([int(e[2]) for e in ev], dtype=np.int32)
+        if any(int(e[1]) != e[1] or int(e[1]) not in (-1, 0, 1) for e in ev):
+            raise ValueError("an event's direction is -1, 0 or 1")
+        if any(int(e[2]) != e[2] or e[2] < 0 for e in ev):
+            raise ValueError("an event's stop count is 0 (never) or a positive integer")
+        if int(self.MaxEventLocs) < 1 or int(self.MaxEventIters) < 1 or not float(self.EventTol) > 0.0:
+            raise ValueError("EventTol must be positive, MaxEventIters and MaxEventLocs at least 1")
+        if (stop > int(self.MaxEventLocs)).any():
+            raise ValueError(f"a stop count exceeds MaxEventLocs = {int(self.MaxEventLocs)}: the stopping occurrence would not be located")
+        return funcs, direction, stop
+
+    def _event_module(self, funcs):
+        key = tuple(id(g) for g in funcs)
+        hit = self._event_modules.get(key)
+        if hit is None or any(a is not b for a, b in zip(hit[1], funcs)):
+            from . import jit
+            hit = (jit.ensure_event_module(self.ode, funcs, compile_only=False), list(funcs))
+            self._event_modules[key] = hit
+        return hit[0]
+
+    def _call_events(self, Y, T, funcs, direction, stop):
+        """asset_hip_propagate_events as it is: dict of xf[m, n], t_end[m], stopped[m], ev_count[m, ne], ev_rows[m, ne, K, n + 1],
+        ev_resid[m, ne, K], ev_conv[m, ne, K], steps[m, 2], status[m]."""
+        m, n, ne, K = Y.shape[0], self.xv, len(funcs), int(self.MaxEventLocs)
+        module = self._event_module(funcs)
+        r = dict(xf=np.empty((m, n)), t_end=np.empty(m), stopped=np.empty(m, dtype=np.int32), ev_count=np.empty((m, ne), dtype=np.int32),
+                 ev_rows=np.empty((m, ne, K, n + 1)), ev_resid=np.empty((m, ne, K)), ev_conv=np.empty((m, ne, K), dtype=np.int32),
+                 steps=np.empty((m, 2), dtype=np.int32), status=np.empty(m, dtype=np.int32))
+        opt, keep = self._c()
+        p = {k: v.ctypes.data_as(_dp if v.dtype == np.float64 else _ip) for k, v in r.items()}
+        _lib.check(_lib.lib().asset_hip_propagate_events(
+            module.encode(), Y.ctypes.data_as(_dp), m, T.ctypes.data_as(_dp), C.byref(opt), ne, direction.ctypes.data_as(_ip),
+            stop.ctypes.data_as(_ip), float(self.EventTol), int(self.MaxEventIters), K, p["xf"], p["t_end"], p["stopped"], p["ev_count"],
+            p["ev_rows"], p["ev_resid"], p["ev_conv"], p["steps"], p["status"], self.device), "asset_hip_propagate_events")
+        del keep
+        return r
+
+    def _propagate_events(self, Y, T, events, details):
+        funcs, direction, stop = self._events(events)
+        m, n, ne, K = Y.shape[0], self.xv, len(funcs), int(self.MaxEventLocs)
+        r = self._call_events(Y, T, funcs, direction, stop)
+        if not details:
+            self._raise_unless_ok(r["status"])
+        rows = Y.copy()
+        rows[:, :n], rows[:, n] = r["xf"], r["t_end"]
+        # full rows for the slots that are used and located, nothing for the others
+        used = (np.arange(K)[None, None, :] < r["ev_count"][:, :, None]) & (r["ev_conv"] != 0)
+        idx = np.argwhere(used)                                                          # (in the order problem, event, occurrence)
+        located = Y[idx[:, 0]]
+        located[:, :n + 1] = r["ev_rows"][idx[:, 0], idx[:, 1], idx[:, 2]]
+        import gc
+        collecting = gc.isenabled()
+        gc.disable()                    # (m (ne + 2) containers, none of them garbage: the collector's passes over them triple the time)
+        try:
+            locs = [[[] for _ in range(ne)] for _ in range(m)]
+            for (i, j), row in zip(idx[:, :2].tolist(), list(located)):
+                locs[i][j].append(row)
+            res = list(zip(list(rows), locs))
+        finally:
+            if collecting:
+                gc.enable()
+        info = {k: r[k] for k in ("steps", "status", "stopped", "t_end", "ev_count", "ev_rows", "ev_resid", "ev_conv")}
+        return res, info
+
     # ---- the reference's methods
-    def integrate(self, x0, tf, details: bool = False):
-        """The end row ``[xf, tf, u, p]``; with ``details`` also (steps[2], status)."""
+    def integrate(self, x0, tf, events=None, details: bool = False):
+        """The end row ``[xf, tf, u, p]``; with ``details`` also (steps[2], status).  With ``events`` (a list of ``(g, direction,
+        stop)``): ``(row, eventlocs)``, the row's time the end time; with ``details`` ``(row, eventlocs, info)``, info the dict of
+        ``integrate_parallel`` for this problem.  ``events`` took the position ``details`` had: a bool as the third positional
+        argument (``integrate(x0, tf, True)``) is still read as ``details``."""
+        if isinstance(events, (bool, np.bool_)):
+            events, details = None, bool(events)
+        if events is not None:
+            r = self.integrate_parallel([x0], [tf], events, details=details)
+            return (r[0][0][0], r[0][0][1], {k: v[0] for k, v in r[1].items()}) if details else r[0]
         r = self.integrate_parallel([x0], [tf], details=details)
         return (r[0][0], r[1][0], int(r[2][0])) if details else r[0]
 
-    def integrate_parallel(self, x0s, tfs, threads=None, details: bool = False):
+    def integrate_parallel(self, x0s, tfs, *args, events=None, threads=None, details: bool = False):
         """A list of end rows, one per initial row (``threads`` is accepted and ignored: the batch is one launch); with ``details``
-        (rows, steps[m, 2], status[m]) and no exception for a failed problem (its states are NaN)."""
+        (rows, steps[m, 2], status[m]) and no exception for a failed problem (its states are NaN).
+        ``integrate_parallel(x0s, tfs, events, threads=None)`` (a list as the third argument, or ``events=``): a list of ``(row,
+        eventlocs)``, ``eventlocs[j]`` the full rows of event j's located occurrences; with ``details`` ``(that list, info)`` with
+        info = dict(steps[m, 2], status[m], stopped[m], t_end[m], ev_count[m, ne], ev_rows[m, ne, MaxEventLocs, XV + 1] -- state and
+        time of every stored occurrence, located or not, NaN where unused --, ev_resid[m, ne, MaxEventLocs], ev_conv[m, ne, MaxEventLocs])."""
+        args = list(args)
+        if args and isinstance(args[0], (list, tuple)):
+            if events is not None:
+                raise TypeError("events given twice")
+            events = args.pop(0)
+        if len(args) > 2:
+            raise TypeError("integrate_parallel(x0s, tfs[, events][, threads][, details])")
+        if len(args) > 1:
+            details = bool(args[1])
         Y, T = self._rows(x0s, tfs)
+        if events is not None:
+            res, info = self._propagate_events(Y, T, events, details)
+            return (res, info) if details else res
         xs, steps, status = self._propagate(Y, T, 1)
         if not details:
             self._raise_unless_ok(status)
         rows = list(self._full_rows(Y, T, xs)[:, 0, :])
         return (rows, steps, status) if details else rows
 
-    def integrate_dense(self, x0, tf, n: int, details: bool = False):
+    @staticmethod
+    def _no_events(what, events):
+        if events is not None:
+            raise NotImplementedError(f"{what} with events is not implemented on the device: events are taken by integrate and "
+                                      "integrate_parallel only")
+
+    def integrate_dense(self, x0, tf, n: int, details: bool = False, events=None):
         """A list of ``n`` rows at equally spaced times from ``t0`` to ``tf`` (the first is ``x0``'s row)."""
+        self._no_events("dense output", events)
         r = self.integrate_dense_parallel([x0], [tf], n, details=details)
         return (r[0][0], r[1][0], int(r[2][0])) if details else r[0]
 
-    def integrate_dense_parallel(self, x0s, tfs, n: int, threads=None, details: bool = False):
+    def integrate_dense_parallel(self, x0s, tfs, n: int, threads=None, details: bool = False, events=None):
         """Per initial row a list of ``n`` rows; with ``details`` (lists, steps, status)."""
+        self._no_events("dense output", events)
         n = int(n)
         if n < 2:
             raise ValueError("a dense integration returns at least two rows")
@@ -153,13 +281,15 @@ class Integrator(IntegratorOptions):
         trajs = [list(tr) for tr in self._full_rows(Y, T, xs)]
         return (trajs, steps, status) if details else trajs
 
-    def integrate_stm(self, x0, tf, details: bool = False):
+    def integrate_stm(self, x0, tf, details: bool = False, events=None):
         """``(xf row, J)``; with ``details`` also (steps[2], status, the end state as the last lane of the lane group holds it)."""
+        self._no_events("the state-transition matrix", events)
         r = self.integrate_stm_parallel([x0], [tf], details=details)
         return (r[0][0][0], r[0][0][1], r[1][0], int(r[2][0]), r[3][0]) if details else r[0]
 
-    def integrate_stm_parallel(self, x0s, tfs, threads=None, details: bool = False):
+    def integrate_stm_parallel(self, x0s, tfs, threads=None, details: bool = False, events=None):
         """A list of ``(xf row, J[XV, XV + 1 + UV + PV + 1])``; with ``details`` (that list, steps[m, 2], status[m], xf_last[m, XV])."""
+        self._no_events("the state-transition matrix", events)
         Y, T = self._rows(x0s, tfs)
         m, n, N = Y.shape[0], self.xv, self._width()
         xf, jac = np.empty((m, 1, n)), np.empty((m, n, N + 1))

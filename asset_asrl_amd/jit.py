@@ -241,6 +241,48 @@ def ensure_bundle(dev_names, compile_only=None) -> str:
                            rtc=(flist, 3, 0, 0, f"ASSET_RTC_BUNDLE({flist})"), compile_only=compile_only)
 
 
+def ensure_event_module(ode, event_funcs, compile_only=None) -> str:
+    """One module that propagates `ode` with the event functions `event_funcs` (1..8 scalar functions of the ODE's input row):
+    csrc/propagate_event_kernels.h: prop_event_kernel<Ode, Ev>; include/asset_hip.h: asset_hip_propagate_events.  The ODE's functor is
+    emitted from ``ode.derivatives()`` as ensure_kernel emits it -- for a library ODE too: both functors have to be in the one
+    translation unit -- and the event functor from the stacked functions (its value is all the kernel calls).  The module is named by a
+    content hash of both; directions and stop counts are arguments of a call, not of the module.  hiprtc only.  Registering the
+    module needs no device (its sizes are read from the code object)."""
+    from . import vf
+    from .vf.codegen import differentiate_function
+    funcs = list(event_funcs)
+    if not 1 <= len(funcs) <= 8:
+        raise ValueError("an event module holds 1..8 event functions")
+    if jit_route() != "hiprtc":
+        raise _lib.AssetHipError("event modules are compiled in process (unset ASSET_HIP_JIT=hipcc)")
+    N = ode.XVars() + 1 + ode.UVars() + ode.PVars()
+    for j, g in enumerate(funcs):
+        if g.IRows() != N:
+            raise ValueError(f"event {j} has {g.IRows()} inputs, the ODE's rows have {N}")
+        if g.ORows() != 1:
+            raise ValueError(f"event {j} is not a scalar function ({g.ORows()} outputs)")
+
+    def maths(text):                                # (the names do not enter the hash, the maths does)
+        return "\n".join(ln for ln in text.splitlines() if "name()" not in ln and not ln.startswith("// generated"))
+
+    d = ode.derivatives()
+    de = differentiate_function("events", vf.stack(funcs) if len(funcs) > 1 else funcs[0])
+    h = hashlib.sha256((maths(emit_hip_functor(d, "OdeUser")) + maths(emit_hip_functor(de, "EvUser"))).encode()).hexdigest()[:12]
+    name = f"events_{_ident(ode.ode_name)}_{h}"
+    if _lib.has_kernel(name, _lib.FUNCTION, False):
+        return name
+    import copy
+    d = copy.copy(d)                                # (the ODE keeps its own record: only the copy is renamed)
+    d.name, de.name = device_name(ode), name
+    so, se = "Ode_" + _ident(d.name), "Ev_" + _ident(name)
+    hdr = ("#include <math.h>\n#include \"" + os.path.join(build.CSRC, "asset_math.h") + "\"\n" + emit_hip_functor(d, so) + "\n"
+           + emit_hip_functor(de, se))
+    flist = f"{so}, {se}"
+    return _build_and_load(name, "events.h", hdr, "events_0", "", _lib.FUNCTION, False,
+                           f"events of ODE '{ode.ode_name}'", rtc=(flist, 4, 0, 0, f"ASSET_RTC_PROP_EVENTS({flist})"),
+                           compile_only=compile_only)
+
+
 def prune_unused(verbose: bool = False, everything: bool = False) -> int:
     """Remove stale code objects from the in-tree module cache: the cache is keyed by content, so builds against older sources
     are never loaded again, but they travel with every snapshot of the tree.  By default only inside the directories of units THIS

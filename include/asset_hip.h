@@ -169,7 +169,7 @@ int asset_hip_kkt_layout(const char* ode, int mode, int blocked, int* nkkt, int*
  * K_FUNC1_ASM / K_FUNC2_ASM, grid_x, block 64, the LDS bytes of the staged block kinds and group = applications per workgroup (64
  * for the unstaged forms); the query by name stays with the transcriptions of an ODE.
  * asset_hip_kernel_slot_kinds: which kinds of run-time module name the slot (bit 0: transcription of an ODE, bit 1: plain
- * function, bit 2: bundle; see asset_hip_jit_compile). */
+ * function, bit 2: bundle, bit 3: an ODE with event functions; see asset_hip_jit_compile). */
 typedef struct asset_hip_plan_step {
   int slot, grid_x, grid_y, block;
   long long lds_bytes;
@@ -363,6 +363,30 @@ int asset_hip_propagate_stm_lanes(const char* ode, const double* y0, long long m
                                   double* xf, double* jac, int* steps, int* status, double* xf_last, int device);
 int asset_hip_propagate_plan(int xv, int uv, int pv, long long m, int stm, long long* out);
 
+/* ---- batched propagation with events ----
+ * Replaces the Events overloads of Integrator::integrate / integrate_parallel (Integrators/Integrator.h:536-730, 1047-1159) for an
+ * integrator without a controller (csrc/propagate_event_kernels.h).  `module` is a run-time module that holds the ODE's functor and
+ * an event functor of ne = 1 .. 8 scalar functions g_j of the ODE's input row (asset_hip_jit_plugin with kind 4); direction[j] in
+ * {-1, 0, 1} and stop[j] >= 0 (0: never stop, k: stop at the k-th occurrence) are arguments of the call, not of the module.  The
+ * step rule and `opt` are asset_hip_propagate's.  After every accepted step event j occurred iff g_j(prev) g_j(next) < 0 and the sign
+ * of g_j(next) matches a non-zero direction; a propagation that stops ends at the END of the accepted step in which an event
+ * reached its stop count.  An occurrence is located on the integrator itself -- one step of size theta h from the start of the
+ * bracketing step, Illinois regula falsi on theta, at most max_event_iters evaluations, done when |g| < event_tol or the bracket's
+ * half-width in time is < event_tol -- and the first max_locs occurrences of every event are stored; later ones are counted only.
+ * Outputs: xf[m][XV] (NaN when status != 0), t_end[m] (tf unless the problem stopped), stopped[m] (the lowest event that reached its
+ * stop count in the last step, else -1), ev_count[m][ne], ev_rows[m][ne][max_locs][XV+1] (state and time, NaN where unused),
+ * ev_resid[m][ne][max_locs] (g at the located point), ev_conv[m][ne][max_locs] (1: located within the tolerance), steps[m][2] and
+ * status[m] as asset_hip_propagate (integration steps only; a stopped problem has status 0; both may be NULL).
+ * asset_hip_event_module_sizes: the sizes of a registered module (no device; any output may be NULL).
+ * Errors, all found before the device is touched: ASSET_HIP_EINVAL (a null pointer, m < 1, ne not the module's, a direction outside
+ * {-1, 0, 1}, stop < 0 or stop > max_locs, event_tol <= 0, max_event_iters < 1, max_locs < 1, a non-finite tf, the option errors of
+ * asset_hip_propagate), ASSET_HIP_ENOODE (no such module), ASSET_HIP_ENODEV.  Nothing is written on an error. */
+int asset_hip_propagate_events(const char* module, const double* y0, long long m, const double* tf, const asset_hip_integ_options* opt,
+                               int ne, const int* direction, const int* stop, double event_tol, int max_event_iters, int max_locs,
+                               double* xf, double* t_end, int* stopped, int* ev_count, double* ev_rows, double* ev_resid, int* ev_conv,
+                               int* steps, int* status, int device);
+int asset_hip_event_module_sizes(const char* module, int* xv, int* uv, int* pv, int* ne);
+
 /* ---- trajectory table: the transcription's own Hermite interpolant of a phase trajectory, on the device ----
  * Replaces LGLInterpTable for exact data (OptimalControl/LGLInterpTable.h:349-372, 480-669, 866-926), the table behind
  * ODEPhaseBase::refineTrajManual / updateMesh / returnTrajRange / returnTrajRangeND / returnTrajTable
@@ -408,7 +432,8 @@ int asset_hip_load_plugin(const char* path);
 /* The same, compiled in process (hiprtc) instead of by the compiler driver.  `source` is the generated translation unit:
  * the functor, `#include "<csrc>/rtc_device.h"` and one ASSET_RTC_LGL(functor, mode, blocked, seg_per_group) or
  * ASSET_RTC_FUNC(functor) line; kind 1 = transcription of an ODE, 2 = plain function, 3 = bundle of plain functions (mode,
- * blocked, seg_per_group ignored); options = hiprtc options ("--offload-arch=gfx950", "-I...", ...).
+ * blocked, seg_per_group ignored), 4 = an ODE with event functions (functor = "Ode, Ev", source ending in
+ * ASSET_RTC_PROP_EVENTS(Ode, Ev); registered WITHOUT a device: its sizes are read from the code object, its first launch loads it); options = hiprtc options ("--offload-arch=gfx950", "-I...", ...).
  *   asset_hip_jit_compile  compiles and writes the code object and the lowered kernel names to cache_path; needs no device.
  *   asset_hip_jit_plugin   registers the module under `name` on the current device: from cache_path when that file
  *                          exists, else by compiling `source` (and writing cache_path when it is not NULL).  0 when
@@ -419,6 +444,10 @@ int asset_hip_jit_compile(const char* source, const char* functor, int kind, int
                           const char* const* options, int noptions, const char* cache_path);
 int asset_hip_jit_plugin(const char* name, const char* source, const char* functor, int kind, int mode, int blocked,
                          int seg_per_group, const char* const* options, int noptions, const char* cache_path);
+/* The meta table (csrc/kernel_meta.h) of a module file written by asset_hip_jit_compile, read on the host from the code object's
+ * image as asset_hip_jit_plugin reads it for kind 4; needs no device.  Returns the number of entries written (meta[0] is the kind) or
+ * ASSET_HIP_EINVAL (no such file, cap too small, an image that is cut short or holds no table). */
+int asset_hip_rtc_module_meta(const char* cache_path, long long* meta, int cap);
 /* collocation weight tables: which in {"tc","s","A","B","U","C","D","E"}; out receives cs or (cs-1) or
  * (cs-1)*cs doubles (row = interior point).  "mesh" (and, with cs = 2, "mesh_trapezoidal"): the scheme of the
  * mesh-error estimator as order, error weight, factorial, xw[cs], dxw[cs].  Returns the count written or <0. */
