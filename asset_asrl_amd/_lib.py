@@ -95,6 +95,12 @@ SYMBOLS = {
                                             C.c_int, C.c_int, _dp, _dp, _ip, _ip, _dp, _dp, _ip, _ip, _ip, C.c_int]),
     "asset_hip_rtc_module_meta": (C.c_int, [C.c_char_p, C.POINTER(C.c_longlong), C.c_int]),
     "asset_hip_event_module_sizes": (C.c_int, [C.c_char_p, _ip, _ip, _ip, _ip]),
+    "asset_hip_propagate_ctrl": (C.c_int, [C.c_char_p, _dp, C.c_longlong, _dp, C.c_int, C.POINTER(IntegOptions), _dp, _dp, _ip, _ip, C.c_int]),
+    "asset_hip_propagate_ctrl_stm": (C.c_int, [C.c_char_p, _dp, C.c_longlong, _dp, C.POINTER(IntegOptions), _dp, _dp, _dp, _ip, _ip,
+                                              C.c_int]),
+    "asset_hip_propagate_ctrl_stm_lanes": (C.c_int, [C.c_char_p, _dp, C.c_longlong, _dp, C.POINTER(IntegOptions), _dp, _dp, _dp, _ip, _ip,
+                                                    _dp, C.c_int]),
+    "asset_hip_controller_module_sizes": (C.c_int, [C.c_char_p, _ip, _ip, _ip]),
     "asset_hip_propagate_plan": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_longlong, C.c_int, C.POINTER(C.c_longlong)]),
     "asset_hip_rk_table": (C.c_int, [C.c_char_p, _dp, C.c_int]),
     "asset_hip_traj_table_create": (C.c_int, [C.c_char_p, C.c_int, C.c_int, _dp, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),

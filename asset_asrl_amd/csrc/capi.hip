@@ -23,6 +23,7 @@
 
 #include "registry.h"
 #include "propagate_event_kernels.h"
+#include "propagate_ctrl_kernels.h"
 #include "capi/kkt_map.h"
 #include "capi/owners.h"
 #include "capi/propagate_plan.h"
@@ -361,7 +362,7 @@ int rtc_compile(const char* source, const char* functor, int kind, int mode, int
 
 int asset_hip_jit_compile(const char* source, const char* functor, int kind, int mode, int blocked, int seg_per_group,
                           const char* const* options, int noptions, const char* cache_path) {
-  if (!source || !functor || !cache_path || kind < 1 || kind > 4) return fail(ASSET_HIP_EINVAL, "bad jit arguments");
+  if (!source || !functor || !cache_path || kind < 1 || kind > 5) return fail(ASSET_HIP_EINVAL, "bad jit arguments");
   RtcBlob blob;
   const int rc = rtc_compile(source, functor, kind, mode, blocked, seg_per_group, options, noptions, blob);
   if (rc) return rc;
@@ -371,7 +372,7 @@ int asset_hip_jit_compile(const char* source, const char* functor, int kind, int
 
 int asset_hip_jit_plugin(const char* name, const char* source, const char* functor, int kind, int mode, int blocked,
                          int seg_per_group, const char* const* options, int noptions, const char* cache_path) {
-  if (!name || !functor || kind < 1 || kind > 4) return fail(ASSET_HIP_EINVAL, "bad jit arguments");
+  if (!name || !functor || kind < 1 || kind > 5) return fail(ASSET_HIP_EINVAL, "bad jit arguments");
   if (find_entry(name, kind >= 2 ? ASSET_HIP_FUNCTION : mode, kind >= 2 ? 0 : blocked)) return 0;
   RtcBlob blob;
   if (!(cache_path && rtc_read(cache_path, blob))) {
@@ -389,8 +390,8 @@ int asset_hip_jit_plugin(const char* name, const char* source, const char* funct
   rtc->code.swap(blob.code);
   rtc->names.swap(blob.names);
   std::unique_ptr<asset_hip::KernelTable> table(new asset_hip::KernelTable());
-  if (kind == 4) {
-    // an ODE with event functions: the table comes from the code object on the host, so that asset_hip_propagate_events can check
+  if (kind >= 4) {
+    // an ODE with event functions, or with a control law: the table comes from the code object on the host, so that asset_hip_propagate_events can check
     // its arguments against it before a device is touched; the module is loaded by its first launch
     if (!rtc_meta_from_code(rtc->code, table->meta))
       return fail(ASSET_HIP_ECOMPILE, "the module has no asset_rtc_meta table of the expected size (rtc_device.h)");
@@ -583,6 +584,8 @@ int asset_hip_defect_create(const asset_hip_defect_desc* d, asset_hip_defect_t* 
   if (ke->table->meta[asset_hip::MF_KIND] == 3) return fail(ASSET_HIP_EINVAL, "a bundle is launched through asset_hip_bundle_*, it is not a function");
   if (ke->table->meta[asset_hip::MF_KIND] == 4)
     return fail(ASSET_HIP_EINVAL, "an event module is launched through asset_hip_propagate_events, it is not a function");
+  if (ke->table->meta[asset_hip::MF_KIND] == 5)
+    return fail(ASSET_HIP_EINVAL, "a controller module is launched through asset_hip_propagate_ctrl*, it is not a function");
   // (before anything is allocated: the commonest set-up error)
   if (const int rc = check_index_tables(ke, d->nseg, d->vindex, d->cindex, d->n_primal, d->n_equal)) return rc;
   if (const int rc = use_device(d->device, "no HIP device visible: the evaluator has no CPU fallback")) return rc;
@@ -666,6 +669,8 @@ int asset_hip_kkt_layout(const char* ode, int mode, int blocked, int* nkkt, int*
   if (!ke) return fail(ASSET_HIP_ENOODE, "no device code compiled for this (ode, mode, blocked)");
   if (ke->table->meta[asset_hip::MF_KIND] == 4)
     return fail(ASSET_HIP_EINVAL, "an event module is launched through asset_hip_propagate_events, it is not a function");
+  if (ke->table->meta[asset_hip::MF_KIND] == 5)
+    return fail(ASSET_HIP_EINVAL, "a controller module is launched through asset_hip_propagate_ctrl*, it is not a function");
   if (nkkt) *nkkt = ke->nkkt;
   return entry_kkt_layout(ke, stride, rows, cols);
 }
@@ -707,6 +712,8 @@ int asset_hip_launch_plan_query(const char* ode, int mode, int blocked, int what
   if (!ke) return fail(ASSET_HIP_ENOODE, "no device code compiled for this (ode, mode, blocked)");
   if (ke->table->meta[asset_hip::MF_KIND] == 4)
     return fail(ASSET_HIP_EINVAL, "an event module is launched through asset_hip_propagate_events, it is not a function");
+  if (ke->table->meta[asset_hip::MF_KIND] == 5)
+    return fail(ASSET_HIP_EINVAL, "a controller module is launched through asset_hip_propagate_ctrl*, it is not a function");
   return entry_launch_plan(ke, what, assembled, nseg, cus, asset_hip::entry_lane_bytes(ke, 0) > 0, out);
 }
 int asset_hip_defect_launch_plan(asset_hip_defect_t h, int what, int assembled, asset_hip_launch_plan* out) {
@@ -716,7 +723,7 @@ int asset_hip_defect_launch_plan(asset_hip_defect_t h, int what, int assembled, 
 const char* asset_hip_kernel_slot_name(int slot) { return asset_hip::kslot_name(slot); }
 int asset_hip_kernel_slot_kinds(int slot) {
   int kinds = 0;
-  for (int kind = 1; kind <= 4; kind++)
+  for (int kind = 1; kind <= 5; kind++)
     if (!asset_hip::rtc_kernel_expr(slot, kind, "F", ASSET_HIP_LGL3, false, 1).empty()) kinds |= 1 << (kind - 1);
   return kinds;
 }
@@ -1054,6 +1061,14 @@ const asset_hip::KernelEntry* event_entry(const char* module) {
   return (ke && ke->table->meta[asset_hip::MF_KIND] == 4 && ke->table->k[asset_hip::K_PROP_EVENT]) ? ke : nullptr;
 }
 
+// an ODE with its control law: a run-time module of kind 5 (asset_hip_jit_plugin), registered under its own name
+const asset_hip::KernelEntry* ctrl_entry(const char* module) {
+  const asset_hip::KernelEntry* ke = find_entry(module, ASSET_HIP_FUNCTION, 0);
+  const bool ok = ke && ke->table->meta[asset_hip::MF_KIND] == 5 && ke->table->k[asset_hip::K_PROP_CTRL_BATCH] &&
+                  ke->table->k[asset_hip::K_PROP_CTRL_STM] && ke->table->k[asset_hip::K_PROP_CTRL_JAC];
+  return ok ? ke : nullptr;
+}
+
 // the option rules of asset_hip_mesh_error_integrator
 int integ_options_checked(const asset_hip_integ_options* opt, asset_hip::IntegOptions& o) {
   o = asset_hip::IntegOptions{0.01, 0.01 / 10000, 0.01 * 10000, 3.0, 1, 100000};
@@ -1227,6 +1242,102 @@ int asset_hip_propagate_events(const char* module, const double* y0, long long m
   HIP_TRY_AS(hipMemcpy(ev_conv, a.ev_conv, sz_e * sizeof(int), hipMemcpyDeviceToHost), "hipMemcpy(ev_conv)");
   if (steps) HIP_TRY_AS(hipMemcpy(steps, a.steps, um * 2 * sizeof(int), hipMemcpyDeviceToHost), "hipMemcpy(steps)");
   if (status) HIP_TRY_AS(hipMemcpy(status, a.status, um * sizeof(int), hipMemcpyDeviceToHost), "hipMemcpy(status)");
+  return 0;
+}
+
+// ---- propagation with a controller (propagate_ctrl_kernels.h).  The checks of propagate_impl, in its order, against a module of kind 5.
+namespace {
+int propagate_ctrl_impl(const char* module, const double* y0, long long m, const double* tf, int ns, const asset_hip_integ_options* opt,
+                        bool stm, double* xs, double* us, double* jac, int* steps, int* status, double* xf_last, int device) {
+  if (!module || !y0 || !tf || !xs || !us || (stm && !jac)) return fail(ASSET_HIP_EINVAL, "null argument");
+  if (m < 1) return fail(ASSET_HIP_EINVAL, "m must be at least 1");
+  if (ns < 1) return fail(ASSET_HIP_EINVAL, "ns must be at least 1");
+  if (!ctrl_entry(module)) {
+    if (find_entry(module, ASSET_HIP_FUNCTION, 0) || prop_entry(module))
+      return fail(ASSET_HIP_ENOODE, std::string("'") + module + "' is not a controller module (asset_hip_jit_plugin, kind 5)");
+    return fail(ASSET_HIP_ENOODE, std::string("no controller module registered as '") + module + "' (asset_hip_jit_plugin, kind 5)");
+  }
+  const asset_hip::KernelEntry* ke = ctrl_entry(module);
+  asset_hip::IntegOptions o;
+  if (const int rc = integ_options_checked(opt, o)) return rc;
+  for (long long i = 0; i < m; i++)
+    if (!std::isfinite(tf[i])) return fail(ASSET_HIP_EINVAL, "tf is not finite (problem " + std::to_string(i) + ")");
+  const int n = ke->xv, uv = ke->uv, N = ke->xv + 1 + ke->uv + ke->pv, C = n + ke->pv;
+  // (a controlled problem carries no control columns: the STM's plan is that of (n, 0, pv))
+  const asset_hip::PropPlan plan = stm ? asset_hip::propagate_plan(n, 0, ke->pv, m, 1) : asset_hip::propagate_plan(n, uv, ke->pv, m, 0);
+  if (plan.grid < 1 || plan.grid > 0x7fffffffLL || size_t(plan.lds_bytes) > 64 * 1024)
+    return fail(ASSET_HIP_EINVAL, "the batch does not fit one launch (workgroups or LDS)");
+  if (const int rc = use_device(device, "no HIP device visible: the propagation has no CPU fallback")) return rc;
+  // one allocation of doubles: y0 | tf | abs | rel | xs | us | (stm: S | jac | xlast); one of ints: steps | status
+  const size_t um = size_t(m), sz_y = um * N, nsu = size_t(stm ? 1 : ns), sz_x = um * nsu * n, sz_u = um * nsu * uv;
+  const size_t sz_s = stm ? um * n * C : 0, sz_j = stm ? um * n * (N + 1) : 0, sz_l = stm ? um * n : 0;
+  DeviceBuffer<double> buf;
+  DeviceBuffer<int> ibuf;
+  HIP_TRY(buf.allocate(sz_y + um + 2 * size_t(n) + sz_x + sz_u + sz_s + sz_j + sz_l));
+  HIP_TRY(ibuf.allocate(um * 3));
+  asset_hip::PropCtrlArgs a;
+  a.m = m, a.ns = stm ? 1 : ns, a.opt = o;
+  a.group = plan.group, a.lanes = plan.lanes, a.passes = plan.passes;
+  double* p = buf.get();
+  double* d_y = p;
+  a.y0 = p, p += sz_y;
+  double* d_tf = p;
+  a.tf = p, p += um;
+  double* d_tols = p;
+  a.abs_tols = p, p += n;
+  a.rel_tols = p, p += n;
+  a.xs = p, p += sz_x;
+  a.us = p, p += sz_u;
+  a.S = stm ? p : nullptr, p += sz_s;
+  a.jac = stm ? p : nullptr, p += sz_j;
+  a.xlast = stm ? p : nullptr;
+  a.steps = ibuf.get(), a.status = ibuf.get() + um * 2;
+  std::vector<double> tols(2 * size_t(n));
+  for (int k = 0; k < n; k++) {
+    tols[k] = (opt && opt->abs_tols) ? opt->abs_tols[k] : 1.0e-12;
+    tols[n + k] = (opt && opt->rel_tols) ? opt->rel_tols[k] : 0.0;
+  }
+  HIP_TRY_AS(hipMemcpy(d_y, y0, sz_y * sizeof(double), hipMemcpyHostToDevice), "hipMemcpy(y0)");
+  HIP_TRY_AS(hipMemcpy(d_tf, tf, um * sizeof(double), hipMemcpyHostToDevice), "hipMemcpy(tf)");
+  HIP_TRY_AS(hipMemcpy(d_tols, tols.data(), tols.size() * sizeof(double), hipMemcpyHostToDevice), "hipMemcpy(tolerances)");
+  void* kargs[] = {&a};
+  const asset_hip::KernelTable& t = *ke->table;
+  HIP_TRY_AS(asset_hip::klaunch(t.k[stm ? asset_hip::K_PROP_CTRL_STM : asset_hip::K_PROP_CTRL_BATCH], dim3(unsigned(plan.grid)), dim3(64),
+                                size_t(plan.lds_bytes), nullptr, kargs), "controller propagation kernel");
+  if (stm)
+    HIP_TRY_AS(asset_hip::klaunch(t.k[asset_hip::K_PROP_CTRL_JAC], dim3(unsigned((m + 63) / 64)), dim3(64), 0, nullptr, kargs),
+               "controller STM assembly kernel");
+  HIP_TRY_AS(hipDeviceSynchronize(), "controller propagation kernels");
+  HIP_TRY_AS(hipMemcpy(xs, a.xs, sz_x * sizeof(double), hipMemcpyDeviceToHost), "hipMemcpy(states)");
+  HIP_TRY_AS(hipMemcpy(us, a.us, sz_u * sizeof(double), hipMemcpyDeviceToHost), "hipMemcpy(controls)");
+  if (stm) HIP_TRY_AS(hipMemcpy(jac, a.jac, sz_j * sizeof(double), hipMemcpyDeviceToHost), "hipMemcpy(jac)");
+  if (stm && xf_last) HIP_TRY_AS(hipMemcpy(xf_last, a.xlast, sz_l * sizeof(double), hipMemcpyDeviceToHost), "hipMemcpy(xf_last)");
+  if (steps) HIP_TRY_AS(hipMemcpy(steps, a.steps, um * 2 * sizeof(int), hipMemcpyDeviceToHost), "hipMemcpy(steps)");
+  if (status) HIP_TRY_AS(hipMemcpy(status, a.status, um * sizeof(int), hipMemcpyDeviceToHost), "hipMemcpy(status)");
+  return 0;
+}
+}  // namespace
+
+int asset_hip_propagate_ctrl(const char* module, const double* y0, long long m, const double* tf, int ns, const asset_hip_integ_options* opt,
+                             double* xs, double* us, int* steps, int* status, int device) {
+  return propagate_ctrl_impl(module, y0, m, tf, ns, opt, false, xs, us, nullptr, steps, status, nullptr, device);
+}
+int asset_hip_propagate_ctrl_stm(const char* module, const double* y0, long long m, const double* tf, const asset_hip_integ_options* opt,
+                                 double* xf, double* uf, double* jac, int* steps, int* status, int device) {
+  return propagate_ctrl_impl(module, y0, m, tf, 1, opt, true, xf, uf, jac, steps, status, nullptr, device);
+}
+int asset_hip_propagate_ctrl_stm_lanes(const char* module, const double* y0, long long m, const double* tf, const asset_hip_integ_options* opt,
+                                       double* xf, double* uf, double* jac, int* steps, int* status, double* xf_last, int device) {
+  if (!xf_last) return fail(ASSET_HIP_EINVAL, "null argument");
+  return propagate_ctrl_impl(module, y0, m, tf, 1, opt, true, xf, uf, jac, steps, status, xf_last, device);
+}
+int asset_hip_controller_module_sizes(const char* module, int* xv, int* uv, int* pv) {
+  if (!module) return fail(ASSET_HIP_EINVAL, "null argument");
+  const asset_hip::KernelEntry* ke = ctrl_entry(module);
+  if (!ke) return fail(ASSET_HIP_ENOODE, std::string("no controller module registered as '") + module + "'");
+  if (xv) *xv = ke->xv;
+  if (uv) *uv = ke->uv;
+  if (pv) *pv = ke->pv;
   return 0;
 }
 

@@ -15,7 +15,7 @@
 namespace asset_hip {
 
 enum MetaField {
-  MF_KIND = 0,       // 1: transcription of an ODE, 2: plain function, 3: bundle of plain functions, 4: an ODE with event functions
+  MF_KIND = 0,       // 1: transcription of an ODE, 2: plain function, 3: bundle of plain functions, 4: an ODE with event functions, 5: an ODE with a control law
   MF_XV, MF_UV, MF_PV,
   MF_MODE,           // ASSET_HIP_* transcription id (0 for plain functions)
   MF_BLOCKED,
@@ -97,6 +97,15 @@ struct BundleMeta {
 template <class Ode, class Ev>
 struct EventMeta {
   static constexpr long long v[MF_COUNT] = {4, Ode::XV, Ode::UV, Ode::PV, 0, 0, Ode::NIN, Ev::XV};
+};
+
+// An ODE with its control law (propagate_ctrl_kernels.h: prop_ctrl_*_kernel<Ode, Ctl>): MF_KIND 5, the ODE's sizes, MF_IR = its input
+// count and MF_OR = the law's outputs (= MF_UV: the functor is refused otherwise at compile time).  Read from the code object on the
+// host, like the table of an event module.
+template <class Ode, class Ctl>
+struct CtrlMeta {
+  static_assert(Ctl::NIN == Ode::NIN && Ctl::XV == Ode::UV, "a control law maps the ODE's input row to its controls");
+  static constexpr long long v[MF_COUNT] = {5, Ode::XV, Ode::UV, Ode::PV, 0, 0, Ode::NIN, Ctl::XV};
 };
 
 }  // namespace asset_hip

@@ -1,9 +1,10 @@
-"""``ode.integrator(...)``: batched propagation of an ODE on the device (csrc/propagate_kernels.h, csrc/propagate_event_kernels.h;
-include/asset_hip.h: asset_hip_propagate, asset_hip_propagate_stm, asset_hip_propagate_events).
+"""``ode.integrator(...)``: batched propagation of an ODE on the device (csrc/propagate_kernels.h, csrc/propagate_event_kernels.h,
+csrc/propagate_ctrl_kernels.h; include/asset_hip.h: asset_hip_propagate, asset_hip_propagate_stm, asset_hip_propagate_events,
+asset_hip_propagate_ctrl, asset_hip_propagate_ctrl_stm).
 
-The reference's ``Integrator`` (Integrators/Integrator.h) in its own method names and return shapes, for the integrator WITHOUT a
-controller: rows go in and come out as full ``[x, t, u, p]`` rows, and the controls and parameters of a row are held for the whole
-propagation (Integrator.h:204-209).  The method is the Prince-Dormand 8(7) pair ("DOPRI87", also "DP87") with the reference's step
+The reference's ``Integrator`` (Integrators/Integrator.h) in its own method names and return shapes: rows go in and come out as full
+``[x, t, u, p]`` rows.  WITHOUT a controller the controls and parameters of a row are held for the whole propagation
+(Integrator.h:204-209); WITH one (below) the controls are a feedback law of the state, the time and the parameters.  The method is the Prince-Dormand 8(7) pair ("DOPRI87", also "DP87") with the reference's step
 controller; the settings are a :class:`~asset_asrl_amd.mesh.IntegratorOptions` -- the reference's setters and defaults
 (Integrator.h:158-172, 297-310) -- plus ``MaxSteps``, this project's cap on accepted + rejected steps of one propagation.
 
@@ -35,8 +36,22 @@ count towards ``stop``.  The event functions are compiled with the ODE into one 
 Locating does not disturb the propagation: the end state and step counts of a problem whose events never stop it are those of the
 call without events, bit for bit.
 
-Out of scope: dense output with events and the STM with events (``NotImplementedError``); ``integrate_stm2`` (second derivatives); controllers other than held controls (a trajectory's control table);
-DOPRI54; ``calc_global_error`` (one serial propagation, not a batch).  ``Phase.AutoScaling`` does not enter: this is an ODE-level
+Controllers (Integrator.h:96-118, 190-249, 373-381, 398-463): ``ode.integrator(def_step, ucon, varlocs)`` -- ``ucon`` a ``vf`` function
+with ``IRows() == len(varlocs)`` and ``ORows() == UV``, ``varlocs`` an int or a sequence of ints indexing the ODE's input row -- evaluates
+``u = ucon(row[varlocs])`` at every Runge-Kutta stage, the row that stage's ``[x_s, t_s, ., p]``; the textbook call is tangential thrust,
+``ode.integrator(.1, Args(3).normalized() * 0.01, [3, 4, 5])``.  The ``u`` columns of the initial rows are ignored, and EVERY returned
+row -- end rows, every dense sample including the first, the STM call's row -- carries the law's value at that row's own state and
+time (the reference's ``update_control``, Integrator.h:462, :557).  The STM keeps its layout; its ``u`` columns are exactly zero (the
+closed loop does not read them), its ``x0`` and ``p`` columns are the exact derivative of the discrete map THROUGH the law with the
+step sequence held fixed, and its time columns are the flow's with the law's controls.  A ``varlocs`` entry inside the control slots
+is refused (``ValueError``): the reference would read a stale value there -- the control of the stage before, or the initial row's.
+The law is compiled with the ODE into one module per (ODE, law, varlocs) at first use (``jit.ensure_controller_module``).
+``ode.integrator(def_step, v)``, ``v`` a number or ``UV`` numbers, is the constant controller (Integrator.h:111-118): ``v`` is written
+into the rows' control columns and the held-control kernels run.
+
+Out of scope: dense output with events and the STM with events (``NotImplementedError``); events with a controller; ``integrate_stm2``
+(second derivatives); the trajectory-table controller ``integrator(def_step, table[, ulocs])`` (a ``u(t)`` law can be written with
+``vf.InterpTable1D``); DOPRI54; ``calc_global_error`` (one serial propagation, not a batch).  ``Phase.AutoScaling`` does not enter: this is an ODE-level
 feature and works in the ODE's own units.
 """
 from __future__ import annotations
@@ -73,15 +88,47 @@ def parse_integrator_args(args):
     return method, float(def_step)
 
 
+def parse_controller_args(ode, args):
+    """(method, def_step, controller) of every constructor form: controller is None (held controls), ``("law", ucon, varlocs)`` or
+    ``("constant", v[UV])``.  Argument errors are raised here, before any device work."""
+    from . import jit
+    from .vf.functions import VectorFunction
+    head = 2 if args and isinstance(args[0], str) else 1
+    if len(args) <= head:
+        return (*parse_integrator_args(args), None)
+    method, def_step = parse_integrator_args(args[:head])
+    rest = args[head:]
+    uv = ode.UVars()
+    if isinstance(rest[0], VectorFunction):
+        if len(rest) != 2:
+            raise TypeError("integrator(def_step, ucon, varlocs): a control law comes with the entries of the input row it reads")
+        return method, def_step, ("law", rest[0], jit.controller_varlocs(ode, rest[0], rest[1]))
+    try:
+        v = np.asarray(rest[0], dtype=np.float64)
+    except (TypeError, ValueError):
+        v = None
+    if v is None or v.ndim > 1 or len(rest) > 1:
+        raise NotImplementedError("integrator(def_step, table[, ulocs]): the trajectory-table controller is not implemented on the device yet "
+                                  "(it is the follow-up of the feedback-law controller); a u(t) law can be written today with the DSL's "
+                                  "InterpTable1D: integrator(def_step, table_as_vf_function_of_t, [t index])")
+    if uv == 0:
+        raise ValueError(f"ODE '{ode.ode_name}' has no controls (UV == 0): there is nothing for a controller to set")
+    v = np.full(uv, float(v)) if v.ndim == 0 else v.copy()
+    if v.size != uv:
+        raise ValueError(f"the constant controller has {v.size} values, the ODE has {uv} controls")
+    return method, def_step, ("constant", v)
+
+
 class Integrator(IntegratorOptions):
     """Returned by ``ODEBase.integrator``.  ``device``: HIP device ordinal of every call."""
 
     def __init__(self, ode, *args, device: int = 0):
-        self.method, def_step = parse_integrator_args(args)
+        self.method, def_step, self.controller = parse_controller_args(ode, args)
         super().__init__(ode.XVars(), def_step)
         self.ode, self.device = ode, int(device)
         self._uv, self._pv = ode.UVars(), ode.PVars()
         self._name = None
+        self._ctrl_module = None
         self.EventTol, self.MaxEventIters, self.MaxEventLocs = 1.0e-6, 10, 8      # Integrator.h:304-305; stored occurrences per event
         self._event_modules = {}
 
@@ -105,7 +152,31 @@ class Integrator(IntegratorOptions):
             raise ValueError(f"{Y.shape[0]} initial rows but {T.size} final times")
         if Y.shape[0] < 1:
             raise ValueError("at least one initial row is needed")
+        if self.controller is not None and self.controller[0] == "constant":      # (the held-control path with u = v)
+            Y = Y.copy()
+            Y[:, self.xv + 1:self.xv + 1 + self._uv] = self.controller[1]
         return Y, T
+
+    def _law(self):
+        return self.controller is not None and self.controller[0] == "law"
+
+    def _controller_module(self):
+        if self._ctrl_module is None:
+            from . import jit
+            self._ctrl_module = jit.ensure_controller_module(self.ode, self.controller[1], self.controller[2], compile_only=False)
+        return self._ctrl_module
+
+    def _propagate_ctrl(self, Y, T, ns):
+        """asset_hip_propagate_ctrl: (xs[m, ns, n], us[m, ns, UV], steps, status)."""
+        m, n = Y.shape[0], self.xv
+        xs, us = np.empty((m, ns, n)), np.empty((m, ns, self._uv))
+        steps, status = np.empty((m, 2), dtype=np.int32), np.empty(m, dtype=np.int32)
+        opt, keep = self._c()
+        _lib.check(_lib.lib().asset_hip_propagate_ctrl(self._controller_module().encode(), Y.ctypes.data_as(_dp), m, T.ctypes.data_as(_dp), int(ns),
+                                                       C.byref(opt), xs.ctypes.data_as(_dp), us.ctypes.data_as(_dp), steps.ctypes.data_as(_ip),
+                                                       status.ctypes.data_as(_ip), self.device), "asset_hip_propagate_ctrl")
+        del keep
+        return xs, us, steps, status
 
     def _raise_unless_ok(self, status):
         bad = np.flatnonzero(status != 0)
@@ -123,11 +194,21 @@ class Integrator(IntegratorOptions):
         del keep
         return xs, steps, status
 
-    def _full_rows(self, Y, T, xs):
-        """[m, ns, N] rows: the states, their times (the kernel's own formula), the row's controls and parameters."""
+    def _states(self, Y, T, ns):
+        """(xs, us or None, steps, status): the controller kernels with a control law, the held-control ones otherwise."""
+        if self._law():
+            return self._propagate_ctrl(Y, T, ns)
+        xs, steps, status = self._propagate(Y, T, ns)
+        return xs, None, steps, status
+
+    def _full_rows(self, Y, T, xs, us=None):
+        """[m, ns, N] rows: the states, their times (the kernel's own formula), the row's controls -- with a control law `us`, the law
+        at every row -- and parameters."""
         m, ns, n = xs.shape
         out = np.repeat(Y[:, None, :], ns, axis=1)
         out[:, :, :n] = xs
+        if us is not None:
+            out[:, :, n + 1:n + 1 + self._uv] = us
         t0, H = Y[:, n], T - Y[:, n]
         if ns == 1:
             out[:, 0, n] = T
@@ -248,12 +329,13 @@ class Integrator(IntegratorOptions):
             details = bool(args[1])
         Y, T = self._rows(x0s, tfs)
         if events is not None:
+            self._no_controller_events()
             res, info = self._propagate_events(Y, T, events, details)
             return (res, info) if details else res
-        xs, steps, status = self._propagate(Y, T, 1)
+        xs, us, steps, status = self._states(Y, T, 1)
         if not details:
             self._raise_unless_ok(status)
-        rows = list(self._full_rows(Y, T, xs)[:, 0, :])
+        rows = list(self._full_rows(Y, T, xs, us)[:, 0, :])
         return (rows, steps, status) if details else rows
 
     @staticmethod
@@ -261,6 +343,11 @@ class Integrator(IntegratorOptions):
         if events is not None:
             raise NotImplementedError(f"{what} with events is not implemented on the device: events are taken by integrate and "
                                       "integrate_parallel only")
+
+    def _no_controller_events(self):
+        if self._law():
+            raise NotImplementedError("events with a controller are not implemented on the device: the event kernel holds a row's controls "
+                                      "(the constant controller integrator(def_step, v) does take events)")
 
     def integrate_dense(self, x0, tf, n: int, details: bool = False, events=None):
         """A list of ``n`` rows at equally spaced times from ``t0`` to ``tf`` (the first is ``x0``'s row)."""
@@ -275,10 +362,10 @@ class Integrator(IntegratorOptions):
         if n < 2:
             raise ValueError("a dense integration returns at least two rows")
         Y, T = self._rows(x0s, tfs)
-        xs, steps, status = self._propagate(Y, T, n)
+        xs, us, steps, status = self._states(Y, T, n)
         if not details:
             self._raise_unless_ok(status)
-        trajs = [list(tr) for tr in self._full_rows(Y, T, xs)]
+        trajs = [list(tr) for tr in self._full_rows(Y, T, xs, us)]
         return (trajs, steps, status) if details else trajs
 
     def integrate_stm(self, x0, tf, details: bool = False, events=None):
@@ -295,16 +382,20 @@ class Integrator(IntegratorOptions):
         xf, jac = np.empty((m, 1, n)), np.empty((m, n, N + 1))
         steps, status = np.empty((m, 2), dtype=np.int32), np.empty(m, dtype=np.int32)
         opt, keep = self._c()
-        head = (self._device_name().encode(), Y.ctypes.data_as(_dp), m, T.ctypes.data_as(_dp), C.byref(opt), xf.ctypes.data_as(_dp),
-                jac.ctypes.data_as(_dp), steps.ctypes.data_as(_ip), status.ctypes.data_as(_ip))
+        law = self._law()
+        uf = np.empty((m, 1, self._uv)) if law else None   # (with a control law: the law at the end row, asset_hip_propagate_ctrl_stm)
+        name = self._controller_module() if law else self._device_name()
+        head = (name.encode(), Y.ctypes.data_as(_dp), m, T.ctypes.data_as(_dp), C.byref(opt), xf.ctypes.data_as(_dp)) \
+            + ((uf.ctypes.data_as(_dp),) if law else ()) + (jac.ctypes.data_as(_dp), steps.ctypes.data_as(_ip), status.ctypes.data_as(_ip))
+        entry = "asset_hip_propagate_ctrl_stm" if law else "asset_hip_propagate_stm"
         if details:                                       # (the diagnostic variant: also the last lane's end state)
             last = np.empty((m, n))
-            _lib.check(_lib.lib().asset_hip_propagate_stm_lanes(*head, last.ctypes.data_as(_dp), self.device), "asset_hip_propagate_stm_lanes")
+            _lib.check(getattr(_lib.lib(), entry + "_lanes")(*head, last.ctypes.data_as(_dp), self.device), entry + "_lanes")
         else:
-            _lib.check(_lib.lib().asset_hip_propagate_stm(*head, self.device), "asset_hip_propagate_stm")
+            _lib.check(getattr(_lib.lib(), entry)(*head, self.device), entry)
         del keep
         if not details:
             self._raise_unless_ok(status)
-        rows = self._full_rows(Y, T, xf)[:, 0, :]
+        rows = self._full_rows(Y, T, xf, uf)[:, 0, :]
         res = [(rows[i], jac[i]) for i in range(m)]
         return (res, steps, status, last) if details else res

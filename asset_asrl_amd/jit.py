@@ -283,6 +283,69 @@ def ensure_event_module(ode, event_funcs, compile_only=None) -> str:
                            compile_only=compile_only)
 
 
+def controller_varlocs(ode, ucon, varlocs):
+    """The checked ``varlocs`` (a list of ints) of a control law ``u = ucon(row[varlocs])`` of `ode`; ``ValueError`` otherwise."""
+    xv, uv, pv = ode.XVars(), ode.UVars(), ode.PVars()
+    N = xv + 1 + uv + pv
+    if uv == 0:
+        raise ValueError(f"ODE '{ode.ode_name}' has no controls (UV == 0): there is nothing for a controller to set")
+    try:
+        locs = [varlocs] if isinstance(varlocs, (int,)) or getattr(varlocs, "ndim", 1) == 0 else list(varlocs)
+        if any(int(v) != v for v in locs):
+            raise TypeError
+        locs = [int(v) for v in locs]
+    except TypeError:
+        raise ValueError("varlocs is an int or a sequence of ints indexing the ODE's input row [x, t, u, p]") from None
+    if ucon.IRows() != len(locs):
+        raise ValueError(f"the control law has {ucon.IRows()} inputs (IRows), varlocs names {len(locs)}")
+    if ucon.ORows() != uv:
+        raise ValueError(f"the control law has {ucon.ORows()} outputs (ORows), the ODE has {uv} controls")
+    for v in locs:
+        if not 0 <= v < N:
+            raise ValueError(f"varlocs entry {v} is out of range: the ODE's input row has {N} entries")
+        if xv + 1 <= v < xv + 1 + uv:
+            raise ValueError(f"varlocs entry {v} lies inside the control slots {xv + 1}..{xv + uv}: the closed loop does not read them")
+    if len(set(locs)) != len(locs):
+        raise ValueError(f"varlocs repeats an entry: {locs}")
+    return locs
+
+
+def ensure_controller_module(ode, ucon, varlocs, compile_only=None) -> str:
+    """One module that propagates `ode` under the control law ``u = ucon(row[varlocs])``: csrc/propagate_ctrl_kernels.h
+    (prop_ctrl_batch_kernel, prop_ctrl_stm_kernel, prop_ctrl_jac_kernel <Ode, Ctl>); include/asset_hip.h: asset_hip_propagate_ctrl*.
+    The ODE's functor is emitted as ensure_event_module emits it; the law's functor is that of ``ucon`` composed with the selection of
+    `varlocs` from the ODE's input row, so it is a function of the FULL row and `varlocs` are compile-time content of the module.  The
+    module is named by a content hash of both functors.  hiprtc only.  Registering the module needs no device."""
+    from . import vf
+    from .vf.codegen import differentiate_function
+    locs = controller_varlocs(ode, ucon, varlocs)
+    if jit_route() != "hiprtc":
+        raise _lib.AssetHipError("controller modules are compiled in process (unset ASSET_HIP_JIT=hipcc)")
+    N = ode.XVars() + 1 + ode.UVars() + ode.PVars()
+    row = vf.Arguments(N)
+    law = ucon.eval(vf.stack([row[v] for v in locs]) if len(locs) > 1 else row[locs[0]])
+
+    def maths(text):                                # (the names do not enter the hash, the maths does)
+        return "\n".join(ln for ln in text.splitlines() if "name()" not in ln and not ln.startswith("// generated"))
+
+    d = ode.derivatives()
+    dc = differentiate_function("controller", law)
+    h = hashlib.sha256((maths(emit_hip_functor(d, "OdeUser")) + maths(emit_hip_functor(dc, "CtlUser"))).encode()).hexdigest()[:12]
+    name = f"ctrl_{_ident(ode.ode_name)}_{h}"
+    if _lib.has_kernel(name, _lib.FUNCTION, False):
+        return name
+    import copy
+    d = copy.copy(d)                                # (the ODE keeps its own record: only the copy is renamed)
+    d.name, dc.name = device_name(ode), name
+    so, sc = "Ode_" + _ident(d.name), "Ctl_" + _ident(name)
+    hdr = ("#include <math.h>\n#include \"" + os.path.join(build.CSRC, "asset_math.h") + "\"\n" + emit_hip_functor(d, so) + "\n"
+           + emit_hip_functor(dc, sc))
+    flist = f"{so}, {sc}"
+    return _build_and_load(name, "controller.h", hdr, "ctrl_0", "", _lib.FUNCTION, False,
+                           f"controller of ODE '{ode.ode_name}'", rtc=(flist, 5, 0, 0, f"ASSET_RTC_PROP_CTRL({flist})"),
+                           compile_only=compile_only)
+
+
 def prune_unused(verbose: bool = False, everything: bool = False) -> int:
     """Remove stale code objects from the in-tree module cache: the cache is keyed by content, so builds against older sources
     are never loaded again, but they travel with every snapshot of the tree.  By default only inside the directories of units THIS

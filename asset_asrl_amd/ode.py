@@ -111,7 +111,15 @@ class ODEBase:
         return ph
 
     def integrator(self, *args, device: int = 0):
-        """``integrator(def_step)`` / ``integrator("DOPRI87", def_step)``: batched propagation on the device (integrator.py)."""
+        """Batched propagation on the device (integrator.py).
+
+        ``integrator(def_step)`` / ``integrator("DOPRI87", def_step)``: a row's controls are held for the whole arc.
+        ``integrator(def_step, ucon, varlocs)`` / ``integrator(method, def_step, ucon, varlocs)``: the controls are the feedback law
+        ``u = ucon(row[varlocs])`` at every Runge-Kutta stage -- ``ucon`` a ``vf`` function with ``IRows() == len(varlocs)`` and
+        ``ORows() == UV``, ``varlocs`` an int or ints indexing the input row ``[x, t, u, p]`` outside its control slots; e.g.
+        tangential thrust, ``integrator(.1, Args(3).normalized() * 0.01, [3, 4, 5])``.  Returned rows carry the law's value.
+        ``integrator(def_step, v)``: the constant controller, ``v`` a number or ``UV`` numbers written into the rows' controls.
+        ``integrator(def_step, table[, ulocs])`` (a trajectory's control table) raises ``NotImplementedError``."""
         from .integrator import Integrator
         return Integrator(self, *args, device=device)
 

@@ -387,6 +387,31 @@ int asset_hip_propagate_events(const char* module, const double* y0, long long m
                                int* steps, int* status, int device);
 int asset_hip_event_module_sizes(const char* module, int* xv, int* uv, int* pv, int* ne);
 
+/* ---- batched propagation with a controller ----
+ * Replaces Integrator::integrate_parallel / integrate_dense_parallel / integrate_stm_parallel for an integrator WITH a controller
+ * (Integrators/Integrator.h:96-118, 190-249, 398-463; csrc/propagate_ctrl_kernels.h).  `module` is a run-time module that holds the
+ * ODE's functor and the functor of a control law u = Ctl(x, t, ., p), a function of the ODE's input row with UV outputs that does not
+ * read the row's control slots (asset_hip_jit_plugin with kind 5).  At every Runge-Kutta stage the controls are the law at the stage's
+ * own state and time; the u columns of y0 are not read.  The step rule, the output times, `opt`, steps and status are
+ * asset_hip_propagate's; a law whose value is not finite gives status 2.
+ *   asset_hip_propagate_ctrl       xs[m][ns][XV] as asset_hip_propagate, and us[m][ns][UV]: the law at every sample's own state and time,
+ *                                  sample 0 included (NaN where the sample was not reached).
+ *   asset_hip_propagate_ctrl_stm   xf[m][XV], uf[m][UV] = the law at (xf, tf), and jac[m][XV][XV+1+UV+PV+1], columns [x0 | t0 | u | p | tf]:
+ *                                  the u columns are exactly zero (the closed loop does not read them), the x0 and p columns are the exact
+ *                                  derivative of the discrete map THROUGH the law with the step sequence held fixed, the time columns the
+ *                                  flow's, -S_x f(x0, t0, Ctl(.), p) and f(xf, tf, Ctl(.), p).  xf and steps are bitwise those of
+ *                                  asset_hip_propagate_ctrl with ns == 1.  ..._stm_lanes: the diagnostic variant with xf_last[m][XV].
+ *   asset_hip_controller_module_sizes  the sizes of a registered module (no device; any output may be NULL).
+ * Errors, all found before the device is touched: those of asset_hip_propagate, and ASSET_HIP_ENOODE when `module` is not registered or
+ * is not a controller module.  Nothing is written on an error. */
+int asset_hip_propagate_ctrl(const char* module, const double* y0, long long m, const double* tf, int ns, const asset_hip_integ_options* opt,
+                             double* xs, double* us, int* steps, int* status, int device);
+int asset_hip_propagate_ctrl_stm(const char* module, const double* y0, long long m, const double* tf, const asset_hip_integ_options* opt,
+                                 double* xf, double* uf, double* jac, int* steps, int* status, int device);
+int asset_hip_propagate_ctrl_stm_lanes(const char* module, const double* y0, long long m, const double* tf, const asset_hip_integ_options* opt,
+                                       double* xf, double* uf, double* jac, int* steps, int* status, double* xf_last, int device);
+int asset_hip_controller_module_sizes(const char* module, int* xv, int* uv, int* pv);
+
 /* ---- trajectory table: the transcription's own Hermite interpolant of a phase trajectory, on the device ----
  * Replaces LGLInterpTable for exact data (OptimalControl/LGLInterpTable.h:349-372, 480-669, 866-926), the table behind
  * ODEPhaseBase::refineTrajManual / updateMesh / returnTrajRange / returnTrajRangeND / returnTrajTable
@@ -433,7 +458,8 @@ int asset_hip_load_plugin(const char* path);
  * the functor, `#include "<csrc>/rtc_device.h"` and one ASSET_RTC_LGL(functor, mode, blocked, seg_per_group) or
  * ASSET_RTC_FUNC(functor) line; kind 1 = transcription of an ODE, 2 = plain function, 3 = bundle of plain functions (mode,
  * blocked, seg_per_group ignored), 4 = an ODE with event functions (functor = "Ode, Ev", source ending in
- * ASSET_RTC_PROP_EVENTS(Ode, Ev); registered WITHOUT a device: its sizes are read from the code object, its first launch loads it); options = hiprtc options ("--offload-arch=gfx950", "-I...", ...).
+ * ASSET_RTC_PROP_EVENTS(Ode, Ev); registered WITHOUT a device: its sizes are read from the code object, its first launch loads it), 5 = an ODE with a control law (functor = "Ode, Ctl", source ending in ASSET_RTC_PROP_CTRL(Ode, Ctl); registered
+ * without a device like kind 4); options = hiprtc options ("--offload-arch=gfx950", "-I...", ...).
  *   asset_hip_jit_compile  compiles and writes the code object and the lowered kernel names to cache_path; needs no device.
  *   asset_hip_jit_plugin   registers the module under `name` on the current device: from cache_path when that file
  *                          exists, else by compiling `source` (and writing cache_path when it is not NULL).  0 when
