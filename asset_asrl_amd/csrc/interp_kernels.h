@@ -106,16 +106,23 @@ struct InterpArgs {
 };
 
 // ---- double-double Horner -------------------------------------------------------------------------------------------
+// The error-free transformations below need every product and sum rounded as written: device code is compiled with
+// -ffp-contract=fast, which turned  r = p + e  into fma(a.h, s, e) and  r - p  into fma(-a.h, s, r)  -- the low part then
+// misses the rounding error of p and the result is no better than plain Horner (tests/test_gpu_traj_table_entries.py saw
+// exactly plain Horner's error).  Contraction is therefore off inside the three functions; the fused multiply-adds that
+// are meant are written as fma().
 struct InterpDD {
   double h, l;
 };
 __device__ inline InterpDD interp_dd_mul(InterpDD a, double s) {   // a * s
+#pragma clang fp contract(off)
   const double p = a.h * s;
   const double e = fma(a.l, s, fma(a.h, s, -p));
   const double r = p + e;
   return {r, e - (r - p)};
 }
 __device__ inline InterpDD interp_dd_add(InterpDD a, double wh, double wl) {   // a + (wh + wl)
+#pragma clang fp contract(off)
   const double s = a.h + wh, bb = s - a.h;
   const double e = ((a.h - (s - bb)) + (wh - bb)) + (a.l + wl);
   const double r = s + e;
@@ -124,6 +131,7 @@ __device__ inline InterpDD interp_dd_add(InterpDD a, double wh, double wl) {   /
 // p(s) and dp/ds of the polynomial with coefficients w[0..NC) (highest power first), each rounded once
 template <int NC>
 __device__ inline void interp_poly(const double* w, double s, double& p, double& dp) {
+#pragma clang fp contract(off)
   InterpDD a{w[0], 0.0}, d{0.0, 0.0};
 #pragma unroll
   for (int k = 1; k < NC; k++) {

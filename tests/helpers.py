@@ -153,6 +153,27 @@ def make_shape(n: int, m: int, p: int):
     return Shape()
 
 
+def make_manyparams(n: int = 3, p: int = 90):
+    """A user-defined ODE with a long parameter vector, (n, 0, p), of which the right-hand side reads n + 2:
+      x_k' = -x_k/2 + sin(x_{k+1}) x_{k+2} p_k + p_{p/2} x_k x_{k+1} + p_{p-1} cos t      (state indices mod n, p/2 rounded down)
+    (3, 0, 90): a trajectory row has N = 94 columns, so stage 1 of the trajectory table (csrc/interp_kernels.h: interp_xdot_kernel)
+    takes its branch without LDS staging, (N|1) + (n|1) = 98 > 96; the shape has device code in Trapezoidal and LGL3 only.  The
+    oracle does not hold it: tests/golden/make_golden_traj_table.py restates it in 50 digits."""
+    from asset_asrl_amd import vf
+    from asset_asrl_amd.ode import ODEArguments, ODEBase
+
+    class ManyParams(ODEBase):
+        def __init__(self):
+            a = ODEArguments(n, 0, p)
+            x = a.XVec().tolist()
+            t = a.TVar()
+            rhs = [-0.5 * x[k] + vf.sin(x[(k + 1) % n]) * x[(k + 2) % n] * a.PVar(k) + a.PVar(p // 2) * x[k] * x[(k + 1) % n]
+                   + a.PVar(p - 1) * vf.cos(t) for k in range(n)]
+            super().__init__(vf.stack(rhs), n, 0, p, name=f"manyparams_{n}_{p}")
+
+    return ManyParams()
+
+
 class FullProblem:
     """One Reentry LGL5 phase with everything a phase can hand the solver: the defect equality, a path equality at every
     state, the mesh-spacing equality of every segment, a pair-wise path inequality between neighbouring states and an
