@@ -977,6 +977,29 @@ int asset_hip_mesh_error_deboor(const char* ode, int mode, int blocked, const do
   return 0;
 }
 
+namespace {
+// the option rules of the integrating entry points; the reference's phase defaults (ODEPhase.h:49; Integrator.h:172, 297-310)
+int integ_options_checked(const asset_hip_integ_options* opt, asset_hip::IntegOptions& o) {
+  o = asset_hip::IntegOptions{0.01, 0.01 / 10000, 0.01 * 10000, 3.0, 1, 100000};
+  if (opt) o = asset_hip::IntegOptions{opt->def_step, opt->min_step, opt->max_step, opt->max_step_change, opt->adaptive != 0, opt->max_steps};
+  if (!(o.def_step > 0.0) || !(o.min_step > 0.0) || !(o.max_step > 0.0)) return fail(ASSET_HIP_EINVAL, "step sizes must be positive");
+  if (o.min_step > o.def_step || o.def_step > o.max_step) return fail(ASSET_HIP_EINVAL, "step sizes must satisfy min <= def <= max");
+  if (!(o.max_step_change > 0.0)) return fail(ASSET_HIP_EINVAL, "max_step_change must be positive");
+  if (o.max_steps < 1) return fail(ASSET_HIP_EINVAL, "max_steps must be at least 1");
+  return 0;
+}
+
+// the tolerances as the kernels read them: abs[n] | rel[n]
+std::vector<double> integ_tols_packed(const asset_hip_integ_options* opt, int n) {
+  std::vector<double> tols(2 * size_t(n));
+  for (int k = 0; k < n; k++) {
+    tols[k] = (opt && opt->abs_tols) ? opt->abs_tols[k] : 1.0e-12;
+    tols[n + k] = (opt && opt->rel_tols) ? opt->rel_tols[k] : 0.0;
+  }
+  return tols;
+}
+}  // namespace
+
 // The integrator-based estimate (integ_kernels.h).  Every input is checked before the device is touched.
 int asset_hip_mesh_error_integrator(const char* ode, int mode, int blocked, const double* traj, int nnodes,
                                     const asset_hip_integ_options* opt, double* tsnd, double* mesh_errors, double* mesh_dist,
@@ -996,13 +1019,8 @@ int asset_hip_mesh_error_integrator(const char* ode, int mode, int blocked, cons
     if (d == 0.0) return fail(ASSET_HIP_EINVAL, "the trajectory holds duplicate times (node " + std::to_string(j) + ")");
     if ((d > 0.0) != (dirn > 0.0)) return fail(ASSET_HIP_EINVAL, "the trajectory's times are not monotonic (node " + std::to_string(j) + ")");
   }
-  // the reference's phase defaults (ODEPhase.h:49; Integrator.h:172, 297-310)
-  asset_hip::IntegOptions o{0.01, 0.01 / 10000, 0.01 * 10000, 3.0, 1, 100000};
-  if (opt) o = asset_hip::IntegOptions{opt->def_step, opt->min_step, opt->max_step, opt->max_step_change, opt->adaptive != 0, opt->max_steps};
-  if (!(o.def_step > 0.0) || !(o.min_step > 0.0) || !(o.max_step > 0.0)) return fail(ASSET_HIP_EINVAL, "step sizes must be positive");
-  if (o.min_step > o.def_step || o.def_step > o.max_step) return fail(ASSET_HIP_EINVAL, "step sizes must satisfy min <= def <= max");
-  if (!(o.max_step_change > 0.0)) return fail(ASSET_HIP_EINVAL, "max_step_change must be positive");
-  if (o.max_steps < 1) return fail(ASSET_HIP_EINVAL, "max_steps must be at least 1");
+  asset_hip::IntegOptions o;
+  if (const int rc = integ_options_checked(opt, o)) return rc;
   if (const int rc = use_device(device, "no HIP device visible: the estimator has no CPU fallback")) return rc;
   // one allocation of doubles: traj | abs | rel | xend | e | tsnd | errors | dist | error_max | dist_max | max_err; one of ints: steps | status
   const size_t sz_traj = size_t(nnodes) * N, sz_x = size_t(nint) * n, sz_e = size_t(nb + 1) * n;
@@ -1027,11 +1045,7 @@ int asset_hip_mesh_error_integrator(const char* ode, int mode, int blocked, cons
   a.dist_max = p, p += nb + 1;
   a.max_err = reinterpret_cast<unsigned long long*>(p);
   a.steps = ibuf.get(), a.status = ibuf.get() + size_t(nint) * 2;
-  std::vector<double> tols(2 * size_t(n));
-  for (int k = 0; k < n; k++) {
-    tols[k] = (opt && opt->abs_tols) ? opt->abs_tols[k] : 1.0e-12;
-    tols[n + k] = (opt && opt->rel_tols) ? opt->rel_tols[k] : 0.0;
-  }
+  const std::vector<double> tols = integ_tols_packed(opt, n);
   HIP_TRY_AS(hipMemcpy(buf.get(), traj, sz_traj * sizeof(double), hipMemcpyHostToDevice), "hipMemcpy(traj)");
   HIP_TRY_AS(hipMemcpy(d_tols, tols.data(), tols.size() * sizeof(double), hipMemcpyHostToDevice), "hipMemcpy(tolerances)");
   HIP_TRY_AS(asset_hip::entry_integ(ke, a, nullptr), "integrator mesh-error kernels");
@@ -1067,17 +1081,6 @@ const asset_hip::KernelEntry* ctrl_entry(const char* module) {
   const bool ok = ke && ke->table->meta[asset_hip::MF_KIND] == 5 && ke->table->k[asset_hip::K_PROP_CTRL_BATCH] &&
                   ke->table->k[asset_hip::K_PROP_CTRL_STM] && ke->table->k[asset_hip::K_PROP_CTRL_JAC];
   return ok ? ke : nullptr;
-}
-
-// the option rules of asset_hip_mesh_error_integrator
-int integ_options_checked(const asset_hip_integ_options* opt, asset_hip::IntegOptions& o) {
-  o = asset_hip::IntegOptions{0.01, 0.01 / 10000, 0.01 * 10000, 3.0, 1, 100000};
-  if (opt) o = asset_hip::IntegOptions{opt->def_step, opt->min_step, opt->max_step, opt->max_step_change, opt->adaptive != 0, opt->max_steps};
-  if (!(o.def_step > 0.0) || !(o.min_step > 0.0) || !(o.max_step > 0.0)) return fail(ASSET_HIP_EINVAL, "step sizes must be positive");
-  if (o.min_step > o.def_step || o.def_step > o.max_step) return fail(ASSET_HIP_EINVAL, "step sizes must satisfy min <= def <= max");
-  if (!(o.max_step_change > 0.0)) return fail(ASSET_HIP_EINVAL, "max_step_change must be positive");
-  if (o.max_steps < 1) return fail(ASSET_HIP_EINVAL, "max_steps must be at least 1");
-  return 0;
 }
 
 int propagate_impl(const char* ode, const double* y0, long long m, const double* tf, int ns, const asset_hip_integ_options* opt, bool stm,
@@ -1119,11 +1122,7 @@ int propagate_impl(const char* ode, const double* y0, long long m, const double*
   a.jac = stm ? p : nullptr, p += sz_j;
   a.xlast = stm ? p : nullptr;
   a.steps = ibuf.get(), a.status = ibuf.get() + um * 2;
-  std::vector<double> tols(2 * size_t(n));
-  for (int k = 0; k < n; k++) {
-    tols[k] = (opt && opt->abs_tols) ? opt->abs_tols[k] : 1.0e-12;
-    tols[n + k] = (opt && opt->rel_tols) ? opt->rel_tols[k] : 0.0;
-  }
+  const std::vector<double> tols = integ_tols_packed(opt, n);
   HIP_TRY_AS(hipMemcpy(d_y, y0, sz_y * sizeof(double), hipMemcpyHostToDevice), "hipMemcpy(y0)");
   HIP_TRY_AS(hipMemcpy(d_tf, tf, um * sizeof(double), hipMemcpyHostToDevice), "hipMemcpy(tf)");
   HIP_TRY_AS(hipMemcpy(d_tols, tols.data(), tols.size() * sizeof(double), hipMemcpyHostToDevice), "hipMemcpy(tolerances)");
@@ -1221,11 +1220,7 @@ int asset_hip_propagate_events(const char* module, const double* y0, long long m
   a.stopped = q, q += um;
   a.ev_count = q, q += sz_c;
   a.ev_conv = q;
-  std::vector<double> tols(2 * size_t(n));
-  for (int k = 0; k < n; k++) {
-    tols[k] = (opt && opt->abs_tols) ? opt->abs_tols[k] : 1.0e-12;
-    tols[n + k] = (opt && opt->rel_tols) ? opt->rel_tols[k] : 0.0;
-  }
+  const std::vector<double> tols = integ_tols_packed(opt, n);
   HIP_TRY_AS(hipMemcpy(d_y, y0, sz_y * sizeof(double), hipMemcpyHostToDevice), "hipMemcpy(y0)");
   HIP_TRY_AS(hipMemcpy(d_tf, tf, um * sizeof(double), hipMemcpyHostToDevice), "hipMemcpy(tf)");
   HIP_TRY_AS(hipMemcpy(d_tols, tols.data(), tols.size() * sizeof(double), hipMemcpyHostToDevice), "hipMemcpy(tolerances)");
@@ -1292,11 +1287,7 @@ int propagate_ctrl_impl(const char* module, const double* y0, long long m, const
   a.jac = stm ? p : nullptr, p += sz_j;
   a.xlast = stm ? p : nullptr;
   a.steps = ibuf.get(), a.status = ibuf.get() + um * 2;
-  std::vector<double> tols(2 * size_t(n));
-  for (int k = 0; k < n; k++) {
-    tols[k] = (opt && opt->abs_tols) ? opt->abs_tols[k] : 1.0e-12;
-    tols[n + k] = (opt && opt->rel_tols) ? opt->rel_tols[k] : 0.0;
-  }
+  const std::vector<double> tols = integ_tols_packed(opt, n);
   HIP_TRY_AS(hipMemcpy(d_y, y0, sz_y * sizeof(double), hipMemcpyHostToDevice), "hipMemcpy(y0)");
   HIP_TRY_AS(hipMemcpy(d_tf, tf, um * sizeof(double), hipMemcpyHostToDevice), "hipMemcpy(tf)");
   HIP_TRY_AS(hipMemcpy(d_tols, tols.data(), tols.size() * sizeof(double), hipMemcpyHostToDevice), "hipMemcpy(tolerances)");
