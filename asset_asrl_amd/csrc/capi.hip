@@ -13,6 +13,7 @@
 #include <string>
 #include <algorithm>
 #include <thread>
+#include <type_traits>
 #include <unordered_map>
 #include <vector>
 
@@ -24,6 +25,7 @@
 #include "registry.h"
 #include "propagate_event_kernels.h"
 #include "propagate_ctrl_kernels.h"
+#include "capi/arena.h"
 #include "capi/kkt_map.h"
 #include "capi/owners.h"
 #include "capi/propagate_plan.h"
@@ -937,46 +939,9 @@ int asset_hip_host_unregister(void* ptr) {
   return 0;
 }
 
-// ---------------------------------------------------------------------------------------------- mesh error estimate
+}  // extern "C"
 
-int asset_hip_mesh_error_deboor(const char* ode, int mode, int blocked, const double* traj, int nnodes, double* tsnd,
-                                double* mesh_errors, double* mesh_dist, double* error_max, double* dist_max,
-                                int device) {
-  if (!ode || !traj || !tsnd || !mesh_errors || !mesh_dist) return fail(ASSET_HIP_EINVAL, "null argument");
-  const asset_hip::KernelEntry* ke = find_entry(ode, mode, blocked);
-  if (!ke) return fail(ASSET_HIP_ENOODE, std::string("no device code compiled for ode='") + ode + "' in this mode");
-  if (!asset_hip::entry_has_mesh(ke)) return fail(ASSET_HIP_EINVAL, "this entry is not a transcription of an ODE");
-  const int cs = asset_hip::mesh_scheme(mode).cs, n = ke->xv, N = ke->xv + 1 + ke->uv + ke->pv;
-  const int nb = (nnodes - 1) / (cs - 1);
-  if (nb < 2 || nb * (cs - 1) + 1 != nnodes)
-    return fail(ASSET_HIP_EINVAL, "the trajectory must hold nb*(cs-1)+1 nodes with nb >= 2 blocks");
-  if (const int rc = use_device(device, "no HIP device visible: the estimator has no CPU fallback")) return rc;
-  // one allocation: traj | yvec | hs | tsnd | errors | dist | error_max | dist_max
-  const size_t sz_traj = size_t(nnodes) * N, sz_y = size_t(nb) * n, sz_e = size_t(nb + 1) * n;
-  const size_t total = sz_traj + sz_y + nb + (nb + 1) + 2 * sz_e + 2 * size_t(nb + 1);
-  DeviceBuffer<double> buf;
-  HIP_TRY(buf.allocate(total));
-  asset_hip::MeshArgs a;
-  a.nb = nb;
-  double* p = buf.get();
-  a.traj = p, p += sz_traj;
-  a.yvec = p, p += sz_y;
-  a.hs = p, p += nb;
-  a.tsnd = p, p += nb + 1;
-  a.errors = p, p += sz_e;
-  a.dist = p, p += sz_e;
-  a.error_max = p, p += nb + 1;
-  a.dist_max = p;
-  HIP_TRY_AS(hipMemcpy(buf.get(), traj, sz_traj * sizeof(double), hipMemcpyHostToDevice), "hipMemcpy(traj)");
-  HIP_TRY_AS(asset_hip::entry_mesh(ke, a, nullptr), "mesh kernels");
-  HIP_TRY_AS(hipMemcpy(tsnd, a.tsnd, (nb + 1) * sizeof(double), hipMemcpyDeviceToHost), "hipMemcpy(results)");
-  HIP_TRY_AS(hipMemcpy(mesh_errors, a.errors, sz_e * sizeof(double), hipMemcpyDeviceToHost), "hipMemcpy(results)");
-  HIP_TRY_AS(hipMemcpy(mesh_dist, a.dist, sz_e * sizeof(double), hipMemcpyDeviceToHost), "hipMemcpy(results)");
-  if (error_max) HIP_TRY_AS(hipMemcpy(error_max, a.error_max, (nb + 1) * sizeof(double), hipMemcpyDeviceToHost), "hipMemcpy(error_max)");
-  if (dist_max) HIP_TRY_AS(hipMemcpy(dist_max, a.dist_max, (nb + 1) * sizeof(double), hipMemcpyDeviceToHost), "hipMemcpy(dist_max)");
-  return 0;
-}
-
+// ------------------------------------------------------------------------- the integrating entry points: their host side
 namespace {
 // the option rules of the integrating entry points; the reference's phase defaults (ODEPhase.h:49; Integrator.h:172, 297-310)
 int integ_options_checked(const asset_hip_integ_options* opt, asset_hip::IntegOptions& o) {
@@ -998,71 +963,80 @@ std::vector<double> integ_tols_packed(const asset_hip_integ_options* opt, int n)
   }
   return tols;
 }
-}  // namespace
 
-// The integrator-based estimate (integ_kernels.h).  Every input is checked before the device is touched.
-int asset_hip_mesh_error_integrator(const char* ode, int mode, int blocked, const double* traj, int nnodes,
-                                    const asset_hip_integ_options* opt, double* tsnd, double* mesh_errors, double* mesh_dist,
-                                    double* error_max, double* dist_max, double* xend, int* steps, int* status, int device) {
-  if (!ode || !traj || !tsnd || !mesh_errors || !mesh_dist) return fail(ASSET_HIP_EINVAL, "null argument");
-  const asset_hip::KernelEntry* ke = find_entry(ode, mode, blocked);
-  if (!ke) return fail(ASSET_HIP_ENOODE, std::string("no device code compiled for ode='") + ode + "' in this mode");
-  if (ke->table->meta[asset_hip::MF_KIND] != 1 || !asset_hip::entry_has_integ(ke))
-    return fail(ASSET_HIP_EINVAL, "this entry is not a transcription of an ODE");
-  const int K = asset_hip::interp_basis(mode).cs - 1, n = ke->xv, N = ke->xv + 1 + ke->uv + ke->pv;
-  if (nnodes < 2 || (nnodes - 1) % K != 0)
-    return fail(ASSET_HIP_EINVAL, "the trajectory must hold nb*(cs-1)+1 nodes with nb >= 1 blocks");
-  const int nb = (nnodes - 1) / K, nint = nnodes - 1;
+// the reference's two checkInput errors (LGLInterpTable.h:147-165) over the times of node rows [x, t, u, p]
+int traj_times_checked(const double* traj, int nnodes, int N, int n) {
   const double dirn = traj[size_t(nnodes - 1) * N + n] - traj[n];
   for (int j = 0; j + 1 < nnodes; j++) {
     const double d = traj[size_t(j + 1) * N + n] - traj[size_t(j) * N + n];
     if (d == 0.0) return fail(ASSET_HIP_EINVAL, "the trajectory holds duplicate times (node " + std::to_string(j) + ")");
     if ((d > 0.0) != (dirn > 0.0)) return fail(ASSET_HIP_EINVAL, "the trajectory's times are not monotonic (node " + std::to_string(j) + ")");
   }
-  asset_hip::IntegOptions o;
-  if (const int rc = integ_options_checked(opt, o)) return rc;
-  if (const int rc = use_device(device, "no HIP device visible: the estimator has no CPU fallback")) return rc;
-  // one allocation of doubles: traj | abs | rel | xend | e | tsnd | errors | dist | error_max | dist_max | max_err; one of ints: steps | status
-  const size_t sz_traj = size_t(nnodes) * N, sz_x = size_t(nint) * n, sz_e = size_t(nb + 1) * n;
-  const size_t total = sz_traj + 2 * size_t(n) + 2 * sz_x + (nb + 1) + 2 * sz_e + 2 * size_t(nb + 1) + 1;
-  DeviceBuffer<double> buf;
-  DeviceBuffer<int> ibuf;
-  HIP_TRY(buf.allocate(total));
-  HIP_TRY(ibuf.allocate(size_t(nint) * 3));
-  asset_hip::IntegArgs a;
-  a.nb = nb, a.opt = o;
-  double* p = buf.get();
-  a.traj = p, p += sz_traj;
-  double* d_tols = p;   // abs | rel
-  a.abs_tols = p, p += n;
-  a.rel_tols = p, p += n;
-  a.xend = p, p += sz_x;
-  a.e = p, p += sz_x;
-  a.tsnd = p, p += nb + 1;
-  a.errors = p, p += sz_e;
-  a.dist = p, p += sz_e;
-  a.error_max = p, p += nb + 1;
-  a.dist_max = p, p += nb + 1;
-  a.max_err = reinterpret_cast<unsigned long long*>(p);
-  a.steps = ibuf.get(), a.status = ibuf.get() + size_t(nint) * 2;
-  const std::vector<double> tols = integ_tols_packed(opt, n);
-  HIP_TRY_AS(hipMemcpy(buf.get(), traj, sz_traj * sizeof(double), hipMemcpyHostToDevice), "hipMemcpy(traj)");
-  HIP_TRY_AS(hipMemcpy(d_tols, tols.data(), tols.size() * sizeof(double), hipMemcpyHostToDevice), "hipMemcpy(tolerances)");
-  HIP_TRY_AS(asset_hip::entry_integ(ke, a, nullptr), "integrator mesh-error kernels");
-  HIP_TRY_AS(hipDeviceSynchronize(), "integrator mesh-error kernels");
-  HIP_TRY_AS(hipMemcpy(tsnd, a.tsnd, (nb + 1) * sizeof(double), hipMemcpyDeviceToHost), "hipMemcpy(results)");
-  HIP_TRY_AS(hipMemcpy(mesh_errors, a.errors, sz_e * sizeof(double), hipMemcpyDeviceToHost), "hipMemcpy(results)");
-  HIP_TRY_AS(hipMemcpy(mesh_dist, a.dist, sz_e * sizeof(double), hipMemcpyDeviceToHost), "hipMemcpy(results)");
-  if (error_max) HIP_TRY_AS(hipMemcpy(error_max, a.error_max, (nb + 1) * sizeof(double), hipMemcpyDeviceToHost), "hipMemcpy(error_max)");
-  if (dist_max) HIP_TRY_AS(hipMemcpy(dist_max, a.dist_max, (nb + 1) * sizeof(double), hipMemcpyDeviceToHost), "hipMemcpy(dist_max)");
-  if (xend) HIP_TRY_AS(hipMemcpy(xend, a.xend, sz_x * sizeof(double), hipMemcpyDeviceToHost), "hipMemcpy(xend)");
-  if (steps) HIP_TRY_AS(hipMemcpy(steps, a.steps, size_t(nint) * 2 * sizeof(int), hipMemcpyDeviceToHost), "hipMemcpy(steps)");
-  if (status) HIP_TRY_AS(hipMemcpy(status, a.status, size_t(nint) * sizeof(int), hipMemcpyDeviceToHost), "hipMemcpy(status)");
   return 0;
 }
 
-// ---------------------------------------------------------------------------------------------- batched propagation
-namespace {
+// The device side of one integrating call.  Every array of the kernels' argument struct is TAKEN from one of two arenas
+// (capi/arena.h: doubles, ints) with its length, once; allocate() makes the one allocation behind each arena, of the size the takes
+// add up to, and points the struct's members into it.  Inputs go in and results come out as tables of rows walked by copy().
+struct IntegCall {
+  asset_hip::Arena<double> d;
+  asset_hip::Arena<int> i;
+  DeviceBuffer<double> dbuf;
+  DeviceBuffer<int> ibuf;
+
+  // `count` elements between a host array (null: the row is skipped) and its place on the device
+  struct Row {
+    void* host;
+    const void* dev;
+    size_t bytes;
+    const char* label;   // hipMemcpy(label) in the error text
+    template <class T>
+    Row(const T* h, const T* dv, size_t count, const char* l) : host(const_cast<T*>(h)), dev(dv), bytes(count * sizeof(T)), label(l) {}
+  };
+
+  int allocate() {
+    if (d.overflowed() || i.overflowed()) return fail(ASSET_HIP_EINVAL, "the arrays of the call do not fit the address space");
+    HIP_TRY_AS(dbuf.allocate(d.total()), "hipMalloc(arrays)");
+    if (i.total()) HIP_TRY_AS(ibuf.allocate(i.total()), "hipMalloc(arrays)");
+    d.bind(dbuf.get()), i.bind(ibuf.get());
+    return 0;
+  }
+  // the rows in order, one blocking copy each
+  static int copy(const std::vector<Row>& rows, hipMemcpyKind kind) {
+    for (const Row& r : rows) {
+      if (!r.host) continue;
+      void* dev = const_cast<void*>(r.dev);
+      const bool in = kind == hipMemcpyHostToDevice;
+      const hipError_t e = hipMemcpy(in ? dev : r.host, in ? r.host : dev, r.bytes, kind);
+      if (e != hipSuccess) return hipfail(e, ("hipMemcpy(" + std::string(r.label) + ")").c_str());
+    }
+    return 0;
+  }
+  // the inputs: node or problem rows (traj, y0), then the final times and the tolerances abs | rel where the call has them
+  static int upload(const double* d_rows, const double* rows, size_t nrows, const char* label, const double* d_abs = nullptr,
+                    const asset_hip_integ_options* opt = nullptr, int n = 0, const double* d_tf = nullptr, const double* tf = nullptr,
+                    size_t m = 0) {
+    const std::vector<double> tols = integ_tols_packed(opt, d_abs ? n : 0);
+    return copy({{rows, d_rows, nrows, label}, {tf, d_tf, m, "tf"}, {d_abs ? tols.data() : nullptr, d_abs, tols.size(), "tolerances"}},
+                hipMemcpyHostToDevice);
+  }
+  static int download(const std::vector<Row>& rows) { return copy(rows, hipMemcpyDeviceToHost); }
+};
+
+// tsnd | errors | dist | error_max | dist_max of an estimator (Args: MeshArgs, IntegArgs): their slots, and their way back
+template <class Args>
+void estimate_take(IntegCall& c, Args& a, int n) {
+  const size_t nd = size_t(a.nb) + 1;
+  c.d.take(&a.tsnd, nd), c.d.take(&a.errors, nd * n), c.d.take(&a.dist, nd * n), c.d.take(&a.error_max, nd), c.d.take(&a.dist_max, nd);
+}
+template <class Args>
+std::vector<IntegCall::Row> estimate_rows(const Args& a, int n, double* tsnd, double* mesh_errors, double* mesh_dist, double* error_max,
+                                          double* dist_max) {
+  const size_t nd = size_t(a.nb) + 1;
+  return {{tsnd, a.tsnd, nd, "results"}, {mesh_errors, a.errors, nd * n, "results"}, {mesh_dist, a.dist, nd * n, "results"},
+          {error_max, a.error_max, nd, "error_max"}, {dist_max, a.dist_max, nd, "dist_max"}};
+}
+
 // the one entry of an ODE that holds its propagation kernels (registry.h: prop_home)
 const asset_hip::KernelEntry* prop_entry(const char* ode) {
   const asset_hip::KernelEntry* ke = find_entry(ode, asset_hip::PROP_HOME_MODE, 0);
@@ -1083,76 +1057,157 @@ const asset_hip::KernelEntry* ctrl_entry(const char* module) {
   return ok ? ke : nullptr;
 }
 
-int propagate_impl(const char* ode, const double* y0, long long m, const double* tf, int ns, const asset_hip_integ_options* opt, bool stm,
-                   double* xs, double* jac, int* steps, int* status, double* xf_last, int device) {
-  if (!ode || !y0 || !tf || !xs || (stm && !jac)) return fail(ASSET_HIP_EINVAL, "null argument");
+// The checks every propagation shares, in their order -- the first that fails wins, all of them before the device is touched.  The
+// caller has checked its pointers; `own` stands where its entry lookup and whatever only it checks come in that order, and gives the
+// launch plan of the entry it found.
+template <class Own>
+int prop_checked(long long m, int ns, const asset_hip_integ_options* opt, const double* tf, int device, asset_hip::IntegOptions& o,
+                 asset_hip::PropPlan& plan, Own own) {
   if (m < 1) return fail(ASSET_HIP_EINVAL, "m must be at least 1");
   if (ns < 1) return fail(ASSET_HIP_EINVAL, "ns must be at least 1");
-  const asset_hip::KernelEntry* ke = prop_entry(ode);
-  if (!ke) return fail(ASSET_HIP_ENOODE, std::string("no propagation kernels compiled for ode='") + ode + "' (its LGL3 entry holds them)");
-  asset_hip::IntegOptions o;
+  if (const int rc = own(plan)) return rc;
   if (const int rc = integ_options_checked(opt, o)) return rc;
   for (long long i = 0; i < m; i++)
     if (!std::isfinite(tf[i])) return fail(ASSET_HIP_EINVAL, "tf is not finite (problem " + std::to_string(i) + ")");
-  const int n = ke->xv, N = ke->xv + 1 + ke->uv + ke->pv, C = N - 1;
-  const asset_hip::PropPlan plan = asset_hip::propagate_plan(ke->xv, ke->uv, ke->pv, m, stm ? 1 : 0);
   if (plan.grid < 1 || plan.grid > 0x7fffffffLL || size_t(plan.lds_bytes) > 64 * 1024)
     return fail(ASSET_HIP_EINVAL, "the batch does not fit one launch (workgroups or LDS)");
-  if (const int rc = use_device(device, "no HIP device visible: the propagation has no CPU fallback")) return rc;
-  // one allocation of doubles: y0 | tf | abs | rel | xs | (stm: S | jac | xlast); one of ints: steps | status
-  const size_t um = size_t(m), sz_y = um * N, sz_x = um * size_t(stm ? 1 : ns) * n;
-  const size_t sz_s = stm ? um * n * C : 0, sz_j = stm ? um * n * (N + 1) : 0, sz_l = stm ? um * n : 0;
-  DeviceBuffer<double> buf;
-  DeviceBuffer<int> ibuf;
-  HIP_TRY(buf.allocate(sz_y + um + 2 * size_t(n) + sz_x + sz_s + sz_j + sz_l));
-  HIP_TRY(ibuf.allocate(um * 3));
-  asset_hip::PropArgs a;
-  a.m = m, a.ns = stm ? 1 : ns, a.opt = o;
+  return use_device(device, "no HIP device visible: the propagation has no CPU fallback");
+}
+
+// y0 | tf | abs | rel at the head of the doubles and steps | status at the head of the ints (Args: PropArgs, PropCtrlArgs, PropEventArgs)
+template <class Args>
+void problems_take(IntegCall& c, Args& a, size_t m, int N, int n) {
+  c.d.take(&a.y0, m * N), c.d.take(&a.tf, m), c.d.take(&a.abs_tols, n), c.d.take(&a.rel_tols, n);
+  c.i.take(&a.steps, m * 2), c.i.take(&a.status, m);
+}
+
+// asset_hip_propagate* (Args = PropArgs: `name` an ODE, no `us`) and asset_hip_propagate_ctrl* (PropCtrlArgs: a module of kind 5)
+template <class Args>
+int propagate_impl(const char* name, const double* y0, long long m, const double* tf, int ns, const asset_hip_integ_options* opt, bool stm,
+                   double* xs, double* us, double* jac, int* steps, int* status, double* xf_last, int device) {
+  constexpr bool ctrl = std::is_same<Args, asset_hip::PropCtrlArgs>::value;
+  if (!name || !y0 || !tf || !xs || (ctrl && !us) || (stm && !jac)) return fail(ASSET_HIP_EINVAL, "null argument");
+  const asset_hip::KernelEntry* ke = nullptr;
+  Args a{};
+  asset_hip::PropPlan plan;
+  const int bad = prop_checked(m, ns, opt, tf, device, a.opt, plan, [&](asset_hip::PropPlan& p) {
+    ke = ctrl ? ctrl_entry(name) : prop_entry(name);
+    if (!ke && !ctrl)
+      return fail(ASSET_HIP_ENOODE, std::string("no propagation kernels compiled for ode='") + name + "' (its LGL3 entry holds them)");
+    if (!ke && (find_entry(name, ASSET_HIP_FUNCTION, 0) || prop_entry(name)))
+      return fail(ASSET_HIP_ENOODE, std::string("'") + name + "' is not a controller module (asset_hip_jit_plugin, kind 5)");
+    if (!ke) return fail(ASSET_HIP_ENOODE, std::string("no controller module registered as '") + name + "' (asset_hip_jit_plugin, kind 5)");
+    // (a controlled problem carries no control columns: the STM's plan is that of (n, 0, pv))
+    p = asset_hip::propagate_plan(ke->xv, ctrl && stm ? 0 : ke->uv, ke->pv, m, stm ? 1 : 0);
+    return 0;
+  });
+  if (bad) return bad;
+  const int n = ke->xv, uv = ke->uv, N = n + 1 + uv + ke->pv, C = ctrl ? n + ke->pv : N - 1;
+  // one allocation of doubles: y0 | tf | abs | rel | xs | (controller: us) | (stm: S | jac | xlast); one of ints: steps | status
+  const size_t um = size_t(m), nsu = stm ? 1 : size_t(ns), sz_x = um * nsu * n, sz_u = ctrl ? um * nsu * uv : 0, sz_l = um * n;
+  a.m = m, a.ns = int(nsu);
   a.group = plan.group, a.lanes = plan.lanes, a.passes = plan.passes;
-  double* p = buf.get();
-  double* d_y = p;
-  a.y0 = p, p += sz_y;
-  double* d_tf = p;
-  a.tf = p, p += um;
-  double* d_tols = p;
-  a.abs_tols = p, p += n;
-  a.rel_tols = p, p += n;
-  a.xs = p, p += sz_x;
-  a.S = stm ? p : nullptr, p += sz_s;
-  a.jac = stm ? p : nullptr, p += sz_j;
-  a.xlast = stm ? p : nullptr;
-  a.steps = ibuf.get(), a.status = ibuf.get() + um * 2;
-  const std::vector<double> tols = integ_tols_packed(opt, n);
-  HIP_TRY_AS(hipMemcpy(d_y, y0, sz_y * sizeof(double), hipMemcpyHostToDevice), "hipMemcpy(y0)");
-  HIP_TRY_AS(hipMemcpy(d_tf, tf, um * sizeof(double), hipMemcpyHostToDevice), "hipMemcpy(tf)");
-  HIP_TRY_AS(hipMemcpy(d_tols, tols.data(), tols.size() * sizeof(double), hipMemcpyHostToDevice), "hipMemcpy(tolerances)");
+  double* d_us = nullptr;
+  IntegCall c;
+  problems_take(c, a, um, N, n);
+  c.d.take(&a.xs, sz_x), c.d.take(ctrl ? &d_us : nullptr, sz_u);
+  if (stm) c.d.take(&a.S, sz_l * C), c.d.take(&a.jac, sz_l * (N + 1)), c.d.take(&a.xlast, sz_l);
+  if (const int rc = c.allocate()) return rc;
+  if (const int rc = c.upload(a.y0, y0, um * N, "y0", a.abs_tols, opt, n, a.tf, tf, um)) return rc;
+  if constexpr (ctrl) a.us = d_us;
   void* kargs[] = {&a};
   const asset_hip::KernelTable& t = *ke->table;
-  HIP_TRY_AS(asset_hip::klaunch(t.k[stm ? asset_hip::K_PROP_STM : asset_hip::K_PROP_BATCH], dim3(unsigned(plan.grid)), dim3(64),
-                                size_t(plan.lds_bytes), nullptr, kargs), "propagation kernel");
-  if (stm) HIP_TRY_AS(asset_hip::klaunch(t.k[asset_hip::K_PROP_JAC], dim3(unsigned((m + 63) / 64)), dim3(64), 0, nullptr, kargs), "STM assembly kernel");
-  HIP_TRY_AS(hipDeviceSynchronize(), "propagation kernels");
-  HIP_TRY_AS(hipMemcpy(xs, a.xs, sz_x * sizeof(double), hipMemcpyDeviceToHost), "hipMemcpy(states)");
-  if (stm) HIP_TRY_AS(hipMemcpy(jac, a.jac, sz_j * sizeof(double), hipMemcpyDeviceToHost), "hipMemcpy(jac)");
-  if (stm && xf_last) HIP_TRY_AS(hipMemcpy(xf_last, a.xlast, sz_l * sizeof(double), hipMemcpyDeviceToHost), "hipMemcpy(xf_last)");
-  if (steps) HIP_TRY_AS(hipMemcpy(steps, a.steps, um * 2 * sizeof(int), hipMemcpyDeviceToHost), "hipMemcpy(steps)");
-  if (status) HIP_TRY_AS(hipMemcpy(status, a.status, um * sizeof(int), hipMemcpyDeviceToHost), "hipMemcpy(status)");
-  return 0;
+  const int k_batch = ctrl ? asset_hip::K_PROP_CTRL_BATCH : asset_hip::K_PROP_BATCH, k_stm = ctrl ? asset_hip::K_PROP_CTRL_STM : asset_hip::K_PROP_STM,
+            k_jac = ctrl ? asset_hip::K_PROP_CTRL_JAC : asset_hip::K_PROP_JAC;
+  HIP_TRY_AS(asset_hip::klaunch(t.k[stm ? k_stm : k_batch], dim3(unsigned(plan.grid)), dim3(64), size_t(plan.lds_bytes), nullptr, kargs),
+             ctrl ? "controller propagation kernel" : "propagation kernel");
+  if (stm)
+    HIP_TRY_AS(asset_hip::klaunch(t.k[k_jac], dim3(unsigned((m + 63) / 64)), dim3(64), 0, nullptr, kargs),
+               ctrl ? "controller STM assembly kernel" : "STM assembly kernel");
+  HIP_TRY_AS(hipDeviceSynchronize(), ctrl ? "controller propagation kernels" : "propagation kernels");
+  return c.download({{xs, a.xs, sz_x, "states"}, {us, d_us, sz_u, "controls"}, {jac, a.jac, sz_l * (N + 1), "jac"},
+                     {xf_last, a.xlast, sz_l, "xf_last"}, {steps, a.steps, um * 2, "steps"}, {status, a.status, um, "status"}});
 }
 }  // namespace
 
+extern "C" {
+
+// ---------------------------------------------------------------------------------------------- mesh error estimate
+
+int asset_hip_mesh_error_deboor(const char* ode, int mode, int blocked, const double* traj, int nnodes, double* tsnd,
+                                double* mesh_errors, double* mesh_dist, double* error_max, double* dist_max,
+                                int device) {
+  if (!ode || !traj || !tsnd || !mesh_errors || !mesh_dist) return fail(ASSET_HIP_EINVAL, "null argument");
+  const asset_hip::KernelEntry* ke = find_entry(ode, mode, blocked);
+  if (!ke) return fail(ASSET_HIP_ENOODE, std::string("no device code compiled for ode='") + ode + "' in this mode");
+  if (!asset_hip::entry_has_mesh(ke)) return fail(ASSET_HIP_EINVAL, "this entry is not a transcription of an ODE");
+  const int cs = asset_hip::mesh_scheme(mode).cs, n = ke->xv, N = ke->xv + 1 + ke->uv + ke->pv;
+  const int nb = (nnodes - 1) / (cs - 1);
+  if (nb < 2 || nb * (cs - 1) + 1 != nnodes)
+    return fail(ASSET_HIP_EINVAL, "the trajectory must hold nb*(cs-1)+1 nodes with nb >= 2 blocks");
+  if (const int rc = use_device(device, "no HIP device visible: the estimator has no CPU fallback")) return rc;
+  // one allocation: traj | yvec | hs | tsnd | errors | dist | error_max | dist_max
+  const size_t sz_traj = size_t(nnodes) * N;
+  asset_hip::MeshArgs a{};
+  a.nb = nb;
+  IntegCall c;
+  c.d.take(&a.traj, sz_traj), c.d.take(&a.yvec, size_t(nb) * n), c.d.take(&a.hs, nb);
+  estimate_take(c, a, n);
+  if (const int rc = c.allocate()) return rc;
+  if (const int rc = c.upload(a.traj, traj, sz_traj, "traj")) return rc;
+  HIP_TRY_AS(asset_hip::entry_mesh(ke, a, nullptr), "mesh kernels");
+  return c.download(estimate_rows(a, n, tsnd, mesh_errors, mesh_dist, error_max, dist_max));
+}
+
+// The integrator-based estimate (integ_kernels.h).  Every input is checked before the device is touched.
+int asset_hip_mesh_error_integrator(const char* ode, int mode, int blocked, const double* traj, int nnodes,
+                                    const asset_hip_integ_options* opt, double* tsnd, double* mesh_errors, double* mesh_dist,
+                                    double* error_max, double* dist_max, double* xend, int* steps, int* status, int device) {
+  if (!ode || !traj || !tsnd || !mesh_errors || !mesh_dist) return fail(ASSET_HIP_EINVAL, "null argument");
+  const asset_hip::KernelEntry* ke = find_entry(ode, mode, blocked);
+  if (!ke) return fail(ASSET_HIP_ENOODE, std::string("no device code compiled for ode='") + ode + "' in this mode");
+  if (ke->table->meta[asset_hip::MF_KIND] != 1 || !asset_hip::entry_has_integ(ke))
+    return fail(ASSET_HIP_EINVAL, "this entry is not a transcription of an ODE");
+  const int K = asset_hip::interp_basis(mode).cs - 1, n = ke->xv, N = ke->xv + 1 + ke->uv + ke->pv;
+  if (nnodes < 2 || (nnodes - 1) % K != 0)
+    return fail(ASSET_HIP_EINVAL, "the trajectory must hold nb*(cs-1)+1 nodes with nb >= 1 blocks");
+  if (const int rc = traj_times_checked(traj, nnodes, N, n)) return rc;
+  asset_hip::IntegArgs a{};
+  a.nb = (nnodes - 1) / K;
+  if (const int rc = integ_options_checked(opt, a.opt)) return rc;
+  if (const int rc = use_device(device, "no HIP device visible: the estimator has no CPU fallback")) return rc;
+  // one allocation of doubles: traj | abs | rel | xend | e | tsnd | errors | dist | error_max | dist_max | max_err; one of ints: steps | status
+  const size_t sz_traj = size_t(nnodes) * N, nint = size_t(nnodes) - 1;
+  double* d_max_err = nullptr;
+  IntegCall c;
+  c.d.take(&a.traj, sz_traj), c.d.take(&a.abs_tols, n), c.d.take(&a.rel_tols, n), c.d.take(&a.xend, nint * n), c.d.take(&a.e, nint * n);
+  estimate_take(c, a, n);
+  c.d.take(&d_max_err, 1);
+  c.i.take(&a.steps, nint * 2), c.i.take(&a.status, nint);
+  if (const int rc = c.allocate()) return rc;
+  a.max_err = reinterpret_cast<unsigned long long*>(d_max_err);
+  if (const int rc = c.upload(a.traj, traj, sz_traj, "traj", a.abs_tols, opt, n)) return rc;
+  HIP_TRY_AS(asset_hip::entry_integ(ke, a, nullptr), "integrator mesh-error kernels");
+  HIP_TRY_AS(hipDeviceSynchronize(), "integrator mesh-error kernels");
+  std::vector<IntegCall::Row> rows = estimate_rows(a, n, tsnd, mesh_errors, mesh_dist, error_max, dist_max);
+  rows.insert(rows.end(), {{xend, a.xend, nint * n, "xend"}, {steps, a.steps, nint * 2, "steps"}, {status, a.status, nint, "status"}});
+  return c.download(rows);
+}
+
+// ---------------------------------------------------------------------------------------------- batched propagation
+
 int asset_hip_propagate(const char* ode, const double* y0, long long m, const double* tf, int ns, const asset_hip_integ_options* opt,
                         double* xs, int* steps, int* status, int device) {
-  return propagate_impl(ode, y0, m, tf, ns, opt, false, xs, nullptr, steps, status, nullptr, device);
+  return propagate_impl<asset_hip::PropArgs>(ode, y0, m, tf, ns, opt, false, xs, nullptr, nullptr, steps, status, nullptr, device);
 }
 int asset_hip_propagate_stm(const char* ode, const double* y0, long long m, const double* tf, const asset_hip_integ_options* opt,
                             double* xf, double* jac, int* steps, int* status, int device) {
-  return propagate_impl(ode, y0, m, tf, 1, opt, true, xf, jac, steps, status, nullptr, device);
+  return propagate_impl<asset_hip::PropArgs>(ode, y0, m, tf, 1, opt, true, xf, nullptr, jac, steps, status, nullptr, device);
 }
 int asset_hip_propagate_stm_lanes(const char* ode, const double* y0, long long m, const double* tf, const asset_hip_integ_options* opt,
                                   double* xf, double* jac, int* steps, int* status, double* xf_last, int device) {
   if (!xf_last) return fail(ASSET_HIP_EINVAL, "null argument");
-  return propagate_impl(ode, y0, m, tf, 1, opt, true, xf, jac, steps, status, xf_last, device);
+  return propagate_impl<asset_hip::PropArgs>(ode, y0, m, tf, 1, opt, true, xf, nullptr, jac, steps, status, xf_last, device);
 }
 int asset_hip_event_module_sizes(const char* module, int* xv, int* uv, int* pv, int* ne) {
   if (!module) return fail(ASSET_HIP_EINVAL, "null argument");
@@ -1171,156 +1226,59 @@ int asset_hip_propagate_events(const char* module, const double* y0, long long m
                                int* steps, int* status, int device) {
   if (!module || !y0 || !tf || !direction || !stop || !xf || !t_end || !stopped || !ev_count || !ev_rows || !ev_resid || !ev_conv)
     return fail(ASSET_HIP_EINVAL, "null argument");
-  if (m < 1) return fail(ASSET_HIP_EINVAL, "m must be at least 1");
-  const asset_hip::KernelEntry* ke = event_entry(module);
-  if (!ke) return fail(ASSET_HIP_ENOODE, std::string("no event module registered as '") + module + "' (asset_hip_jit_plugin, kind 4)");
-  if (ne != ke->orr) return fail(ASSET_HIP_EINVAL, "ne is " + std::to_string(ne) + " but the module has " + std::to_string(ke->orr) + " events");
-  if (!(event_tol > 0.0)) return fail(ASSET_HIP_EINVAL, "event_tol must be positive");
-  if (max_event_iters < 1) return fail(ASSET_HIP_EINVAL, "max_event_iters must be at least 1");
-  if (max_locs < 1) return fail(ASSET_HIP_EINVAL, "max_locs must be at least 1");
-  for (int j = 0; j < ne; j++) {
-    if (direction[j] < -1 || direction[j] > 1) return fail(ASSET_HIP_EINVAL, "direction must be -1, 0 or 1 (event " + std::to_string(j) + ")");
-    if (stop[j] < 0) return fail(ASSET_HIP_EINVAL, "stop must not be negative (event " + std::to_string(j) + ")");
-    if (stop[j] > max_locs)
-      return fail(ASSET_HIP_EINVAL, "stop exceeds max_locs: the stopping occurrence would not be located (event " + std::to_string(j) + ")");
-  }
-  asset_hip::IntegOptions o;
-  if (const int rc = integ_options_checked(opt, o)) return rc;
-  for (long long i = 0; i < m; i++)
-    if (!std::isfinite(tf[i])) return fail(ASSET_HIP_EINVAL, "tf is not finite (problem " + std::to_string(i) + ")");
+  const asset_hip::KernelEntry* ke = nullptr;
+  asset_hip::PropEventArgs a{};
+  asset_hip::PropPlan plan;
+  const int bad = prop_checked(m, 1, opt, tf, device, a.opt, plan, [&](asset_hip::PropPlan& p) {
+    ke = event_entry(module);
+    if (!ke) return fail(ASSET_HIP_ENOODE, std::string("no event module registered as '") + module + "' (asset_hip_jit_plugin, kind 4)");
+    if (ne != ke->orr) return fail(ASSET_HIP_EINVAL, "ne is " + std::to_string(ne) + " but the module has " + std::to_string(ke->orr) + " events");
+    if (!(event_tol > 0.0)) return fail(ASSET_HIP_EINVAL, "event_tol must be positive");
+    if (max_event_iters < 1) return fail(ASSET_HIP_EINVAL, "max_event_iters must be at least 1");
+    if (max_locs < 1) return fail(ASSET_HIP_EINVAL, "max_locs must be at least 1");
+    for (int j = 0; j < ne; j++) {
+      if (direction[j] < -1 || direction[j] > 1) return fail(ASSET_HIP_EINVAL, "direction must be -1, 0 or 1 (event " + std::to_string(j) + ")");
+      if (stop[j] < 0) return fail(ASSET_HIP_EINVAL, "stop must not be negative (event " + std::to_string(j) + ")");
+      if (stop[j] > max_locs)
+        return fail(ASSET_HIP_EINVAL, "stop exceeds max_locs: the stopping occurrence would not be located (event " + std::to_string(j) + ")");
+    }
+    p = asset_hip::propagate_plan(ke->xv, ke->uv, ke->pv, m, 0);
+    return 0;
+  });
+  if (bad) return bad;
   const int n = ke->xv, N = ke->xv + 1 + ke->uv + ke->pv;
-  const asset_hip::PropPlan plan = asset_hip::propagate_plan(ke->xv, ke->uv, ke->pv, m, 0);
-  if (plan.grid < 1 || plan.grid > 0x7fffffffLL || size_t(plan.lds_bytes) > 64 * 1024)
-    return fail(ASSET_HIP_EINVAL, "the batch does not fit one launch (workgroups or LDS)");
-  if (const int rc = use_device(device, "no HIP device visible: the propagation has no CPU fallback")) return rc;
   // one allocation of doubles: y0 | tf | abs | rel | xf | t_end | ev_rows | ev_resid; one of ints: steps | status | stopped | ev_count | ev_conv
-  const size_t um = size_t(m), sz_y = um * N, sz_x = um * n, sz_e = um * ne * size_t(max_locs), sz_r = sz_e * (n + 1), sz_c = um * ne;
-  DeviceBuffer<double> buf;
-  DeviceBuffer<int> ibuf;
-  HIP_TRY(buf.allocate(sz_y + um + 2 * size_t(n) + sz_x + um + sz_r + sz_e));
-  HIP_TRY(ibuf.allocate(um * 4 + sz_c + sz_e));
-  asset_hip::PropEventArgs a;
-  a.m = m, a.lanes = plan.lanes, a.max_iters = max_event_iters, a.max_locs = max_locs, a.event_tol = event_tol, a.opt = o;
+  const size_t um = size_t(m), sz_x = um * n, sz_e = um * ne * size_t(max_locs), sz_r = sz_e * (n + 1), sz_c = um * ne;
+  a.m = m, a.lanes = plan.lanes, a.max_iters = max_event_iters, a.max_locs = max_locs, a.event_tol = event_tol;
   for (int j = 0; j < asset_hip::PROP_EVENT_MAX; j++) a.direction[j] = j < ne ? direction[j] : 0, a.stop[j] = j < ne ? stop[j] : 0;
-  double* p = buf.get();
-  double* d_y = p;
-  a.y0 = p, p += sz_y;
-  double* d_tf = p;
-  a.tf = p, p += um;
-  double* d_tols = p;
-  a.abs_tols = p, p += n;
-  a.rel_tols = p, p += n;
-  a.xf = p, p += sz_x;
-  a.t_end = p, p += um;
-  a.ev_rows = p, p += sz_r;
-  a.ev_resid = p;
-  int* q = ibuf.get();
-  a.steps = q, q += um * 2;
-  a.status = q, q += um;
-  a.stopped = q, q += um;
-  a.ev_count = q, q += sz_c;
-  a.ev_conv = q;
-  const std::vector<double> tols = integ_tols_packed(opt, n);
-  HIP_TRY_AS(hipMemcpy(d_y, y0, sz_y * sizeof(double), hipMemcpyHostToDevice), "hipMemcpy(y0)");
-  HIP_TRY_AS(hipMemcpy(d_tf, tf, um * sizeof(double), hipMemcpyHostToDevice), "hipMemcpy(tf)");
-  HIP_TRY_AS(hipMemcpy(d_tols, tols.data(), tols.size() * sizeof(double), hipMemcpyHostToDevice), "hipMemcpy(tolerances)");
+  IntegCall c;
+  problems_take(c, a, um, N, n);
+  c.d.take(&a.xf, sz_x), c.d.take(&a.t_end, um), c.d.take(&a.ev_rows, sz_r), c.d.take(&a.ev_resid, sz_e);
+  c.i.take(&a.stopped, um), c.i.take(&a.ev_count, sz_c), c.i.take(&a.ev_conv, sz_e);
+  if (const int rc = c.allocate()) return rc;
+  if (const int rc = c.upload(a.y0, y0, um * N, "y0", a.abs_tols, opt, n, a.tf, tf, um)) return rc;
   void* kargs[] = {&a};
   HIP_TRY_AS(asset_hip::klaunch(ke->table->k[asset_hip::K_PROP_EVENT], dim3(unsigned(plan.grid)), dim3(64), size_t(plan.lds_bytes), nullptr,
                                 kargs), "event propagation kernel");
   HIP_TRY_AS(hipDeviceSynchronize(), "event propagation kernel");
-  HIP_TRY_AS(hipMemcpy(xf, a.xf, sz_x * sizeof(double), hipMemcpyDeviceToHost), "hipMemcpy(states)");
-  HIP_TRY_AS(hipMemcpy(t_end, a.t_end, um * sizeof(double), hipMemcpyDeviceToHost), "hipMemcpy(t_end)");
-  HIP_TRY_AS(hipMemcpy(ev_rows, a.ev_rows, sz_r * sizeof(double), hipMemcpyDeviceToHost), "hipMemcpy(ev_rows)");
-  HIP_TRY_AS(hipMemcpy(ev_resid, a.ev_resid, sz_e * sizeof(double), hipMemcpyDeviceToHost), "hipMemcpy(ev_resid)");
-  HIP_TRY_AS(hipMemcpy(stopped, a.stopped, um * sizeof(int), hipMemcpyDeviceToHost), "hipMemcpy(stopped)");
-  HIP_TRY_AS(hipMemcpy(ev_count, a.ev_count, sz_c * sizeof(int), hipMemcpyDeviceToHost), "hipMemcpy(ev_count)");
-  HIP_TRY_AS(hipMemcpy(ev_conv, a.ev_conv, sz_e * sizeof(int), hipMemcpyDeviceToHost), "hipMemcpy(ev_conv)");
-  if (steps) HIP_TRY_AS(hipMemcpy(steps, a.steps, um * 2 * sizeof(int), hipMemcpyDeviceToHost), "hipMemcpy(steps)");
-  if (status) HIP_TRY_AS(hipMemcpy(status, a.status, um * sizeof(int), hipMemcpyDeviceToHost), "hipMemcpy(status)");
-  return 0;
+  return c.download({{xf, a.xf, sz_x, "states"}, {t_end, a.t_end, um, "t_end"}, {ev_rows, a.ev_rows, sz_r, "ev_rows"},
+                     {ev_resid, a.ev_resid, sz_e, "ev_resid"}, {stopped, a.stopped, um, "stopped"}, {ev_count, a.ev_count, sz_c, "ev_count"},
+                     {ev_conv, a.ev_conv, sz_e, "ev_conv"}, {steps, a.steps, um * 2, "steps"}, {status, a.status, um, "status"}});
 }
 
-// ---- propagation with a controller (propagate_ctrl_kernels.h).  The checks of propagate_impl, in its order, against a module of kind 5.
-namespace {
-int propagate_ctrl_impl(const char* module, const double* y0, long long m, const double* tf, int ns, const asset_hip_integ_options* opt,
-                        bool stm, double* xs, double* us, double* jac, int* steps, int* status, double* xf_last, int device) {
-  if (!module || !y0 || !tf || !xs || !us || (stm && !jac)) return fail(ASSET_HIP_EINVAL, "null argument");
-  if (m < 1) return fail(ASSET_HIP_EINVAL, "m must be at least 1");
-  if (ns < 1) return fail(ASSET_HIP_EINVAL, "ns must be at least 1");
-  if (!ctrl_entry(module)) {
-    if (find_entry(module, ASSET_HIP_FUNCTION, 0) || prop_entry(module))
-      return fail(ASSET_HIP_ENOODE, std::string("'") + module + "' is not a controller module (asset_hip_jit_plugin, kind 5)");
-    return fail(ASSET_HIP_ENOODE, std::string("no controller module registered as '") + module + "' (asset_hip_jit_plugin, kind 5)");
-  }
-  const asset_hip::KernelEntry* ke = ctrl_entry(module);
-  asset_hip::IntegOptions o;
-  if (const int rc = integ_options_checked(opt, o)) return rc;
-  for (long long i = 0; i < m; i++)
-    if (!std::isfinite(tf[i])) return fail(ASSET_HIP_EINVAL, "tf is not finite (problem " + std::to_string(i) + ")");
-  const int n = ke->xv, uv = ke->uv, N = ke->xv + 1 + ke->uv + ke->pv, C = n + ke->pv;
-  // (a controlled problem carries no control columns: the STM's plan is that of (n, 0, pv))
-  const asset_hip::PropPlan plan = stm ? asset_hip::propagate_plan(n, 0, ke->pv, m, 1) : asset_hip::propagate_plan(n, uv, ke->pv, m, 0);
-  if (plan.grid < 1 || plan.grid > 0x7fffffffLL || size_t(plan.lds_bytes) > 64 * 1024)
-    return fail(ASSET_HIP_EINVAL, "the batch does not fit one launch (workgroups or LDS)");
-  if (const int rc = use_device(device, "no HIP device visible: the propagation has no CPU fallback")) return rc;
-  // one allocation of doubles: y0 | tf | abs | rel | xs | us | (stm: S | jac | xlast); one of ints: steps | status
-  const size_t um = size_t(m), sz_y = um * N, nsu = size_t(stm ? 1 : ns), sz_x = um * nsu * n, sz_u = um * nsu * uv;
-  const size_t sz_s = stm ? um * n * C : 0, sz_j = stm ? um * n * (N + 1) : 0, sz_l = stm ? um * n : 0;
-  DeviceBuffer<double> buf;
-  DeviceBuffer<int> ibuf;
-  HIP_TRY(buf.allocate(sz_y + um + 2 * size_t(n) + sz_x + sz_u + sz_s + sz_j + sz_l));
-  HIP_TRY(ibuf.allocate(um * 3));
-  asset_hip::PropCtrlArgs a;
-  a.m = m, a.ns = stm ? 1 : ns, a.opt = o;
-  a.group = plan.group, a.lanes = plan.lanes, a.passes = plan.passes;
-  double* p = buf.get();
-  double* d_y = p;
-  a.y0 = p, p += sz_y;
-  double* d_tf = p;
-  a.tf = p, p += um;
-  double* d_tols = p;
-  a.abs_tols = p, p += n;
-  a.rel_tols = p, p += n;
-  a.xs = p, p += sz_x;
-  a.us = p, p += sz_u;
-  a.S = stm ? p : nullptr, p += sz_s;
-  a.jac = stm ? p : nullptr, p += sz_j;
-  a.xlast = stm ? p : nullptr;
-  a.steps = ibuf.get(), a.status = ibuf.get() + um * 2;
-  const std::vector<double> tols = integ_tols_packed(opt, n);
-  HIP_TRY_AS(hipMemcpy(d_y, y0, sz_y * sizeof(double), hipMemcpyHostToDevice), "hipMemcpy(y0)");
-  HIP_TRY_AS(hipMemcpy(d_tf, tf, um * sizeof(double), hipMemcpyHostToDevice), "hipMemcpy(tf)");
-  HIP_TRY_AS(hipMemcpy(d_tols, tols.data(), tols.size() * sizeof(double), hipMemcpyHostToDevice), "hipMemcpy(tolerances)");
-  void* kargs[] = {&a};
-  const asset_hip::KernelTable& t = *ke->table;
-  HIP_TRY_AS(asset_hip::klaunch(t.k[stm ? asset_hip::K_PROP_CTRL_STM : asset_hip::K_PROP_CTRL_BATCH], dim3(unsigned(plan.grid)), dim3(64),
-                                size_t(plan.lds_bytes), nullptr, kargs), "controller propagation kernel");
-  if (stm)
-    HIP_TRY_AS(asset_hip::klaunch(t.k[asset_hip::K_PROP_CTRL_JAC], dim3(unsigned((m + 63) / 64)), dim3(64), 0, nullptr, kargs),
-               "controller STM assembly kernel");
-  HIP_TRY_AS(hipDeviceSynchronize(), "controller propagation kernels");
-  HIP_TRY_AS(hipMemcpy(xs, a.xs, sz_x * sizeof(double), hipMemcpyDeviceToHost), "hipMemcpy(states)");
-  HIP_TRY_AS(hipMemcpy(us, a.us, sz_u * sizeof(double), hipMemcpyDeviceToHost), "hipMemcpy(controls)");
-  if (stm) HIP_TRY_AS(hipMemcpy(jac, a.jac, sz_j * sizeof(double), hipMemcpyDeviceToHost), "hipMemcpy(jac)");
-  if (stm && xf_last) HIP_TRY_AS(hipMemcpy(xf_last, a.xlast, sz_l * sizeof(double), hipMemcpyDeviceToHost), "hipMemcpy(xf_last)");
-  if (steps) HIP_TRY_AS(hipMemcpy(steps, a.steps, um * 2 * sizeof(int), hipMemcpyDeviceToHost), "hipMemcpy(steps)");
-  if (status) HIP_TRY_AS(hipMemcpy(status, a.status, um * sizeof(int), hipMemcpyDeviceToHost), "hipMemcpy(status)");
-  return 0;
-}
-}  // namespace
-
+// ---- propagation with a controller (propagate_ctrl_kernels.h): propagate_impl against a module of kind 5
 int asset_hip_propagate_ctrl(const char* module, const double* y0, long long m, const double* tf, int ns, const asset_hip_integ_options* opt,
                              double* xs, double* us, int* steps, int* status, int device) {
-  return propagate_ctrl_impl(module, y0, m, tf, ns, opt, false, xs, us, nullptr, steps, status, nullptr, device);
+  return propagate_impl<asset_hip::PropCtrlArgs>(module, y0, m, tf, ns, opt, false, xs, us, nullptr, steps, status, nullptr, device);
 }
 int asset_hip_propagate_ctrl_stm(const char* module, const double* y0, long long m, const double* tf, const asset_hip_integ_options* opt,
                                  double* xf, double* uf, double* jac, int* steps, int* status, int device) {
-  return propagate_ctrl_impl(module, y0, m, tf, 1, opt, true, xf, uf, jac, steps, status, nullptr, device);
+  return propagate_impl<asset_hip::PropCtrlArgs>(module, y0, m, tf, 1, opt, true, xf, uf, jac, steps, status, nullptr, device);
 }
 int asset_hip_propagate_ctrl_stm_lanes(const char* module, const double* y0, long long m, const double* tf, const asset_hip_integ_options* opt,
                                        double* xf, double* uf, double* jac, int* steps, int* status, double* xf_last, int device) {
   if (!xf_last) return fail(ASSET_HIP_EINVAL, "null argument");
-  return propagate_ctrl_impl(module, y0, m, tf, 1, opt, true, xf, uf, jac, steps, status, xf_last, device);
+  return propagate_impl<asset_hip::PropCtrlArgs>(module, y0, m, tf, 1, opt, true, xf, uf, jac, steps, status, xf_last, device);
 }
 int asset_hip_controller_module_sizes(const char* module, int* xv, int* uv, int* pv) {
   if (!module) return fail(ASSET_HIP_EINVAL, "null argument");
@@ -1384,13 +1342,7 @@ int asset_hip_traj_table_create(const char* ode, int mode, int blocked, const do
   const int nb = (nnodes - 1) / K;
   for (size_t i = 0, e = size_t(nnodes) * N; i < e; i++)
     if (!std::isfinite(traj[i])) return fail(ASSET_HIP_EINVAL, "NaN or Inf in the trajectory");
-  // the reference's two checkInput errors (LGLInterpTable.h:147-165)
-  const double dirn = traj[size_t(nnodes - 1) * N + n] - traj[n];
-  for (int j = 0; j + 1 < nnodes; j++) {
-    const double d = traj[size_t(j + 1) * N + n] - traj[size_t(j) * N + n];
-    if (d == 0.0) return fail(ASSET_HIP_EINVAL, "the trajectory holds duplicate times (node " + std::to_string(j) + ")");
-    if ((d > 0.0) != (dirn > 0.0)) return fail(ASSET_HIP_EINVAL, "the trajectory's times are not monotonic (node " + std::to_string(j) + ")");
-  }
+  if (const int rc = traj_times_checked(traj, nnodes, N, n)) return rc;
   if (const int rc = use_device(device, "no HIP device visible: the trajectory table has no CPU fallback")) return rc;
   std::unique_ptr<asset_hip_traj_table> t(new (std::nothrow) asset_hip_traj_table());
   if (!t) return fail(ASSET_HIP_EINVAL, "out of host memory");

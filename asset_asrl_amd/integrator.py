@@ -166,16 +166,23 @@ class Integrator(IntegratorOptions):
             self._ctrl_module = jit.ensure_controller_module(self.ode, self.controller[1], self.controller[2], compile_only=False)
         return self._ctrl_module
 
+    def _call(self, entry, name, Y, T, ns, *rest):
+        """One integrating entry point of the C ABI: its shared head (name, rows, m, final times, ``ns`` where it has one, options),
+        then ``rest`` -- arrays go as pointers, anything else as it is -- and the device.  ``name``: a registered name, or the method
+        that gives it (compiling at first use), called once the options have been accepted."""
+        opt, keep = self._c()
+        name = name() if callable(name) else name
+        head = (name.encode(), Y.ctypes.data_as(_dp), Y.shape[0], T.ctypes.data_as(_dp)) + (() if ns is None else (int(ns),))
+        rest = [v.ctypes.data_as(_dp if v.dtype == np.float64 else _ip) if isinstance(v, np.ndarray) else v for v in rest]
+        _lib.check(getattr(_lib.lib(), entry)(*head, C.byref(opt), *rest, self.device), entry)
+        del keep
+
     def _propagate_ctrl(self, Y, T, ns):
         """asset_hip_propagate_ctrl: (xs[m, ns, n], us[m, ns, UV], steps, status)."""
         m, n = Y.shape[0], self.xv
         xs, us = np.empty((m, ns, n)), np.empty((m, ns, self._uv))
         steps, status = np.empty((m, 2), dtype=np.int32), np.empty(m, dtype=np.int32)
-        opt, keep = self._c()
-        _lib.check(_lib.lib().asset_hip_propagate_ctrl(self._controller_module().encode(), Y.ctypes.data_as(_dp), m, T.ctypes.data_as(_dp), int(ns),
-                                                       C.byref(opt), xs.ctypes.data_as(_dp), us.ctypes.data_as(_dp), steps.ctypes.data_as(_ip),
-                                                       status.ctypes.data_as(_ip), self.device), "asset_hip_propagate_ctrl")
-        del keep
+        self._call("asset_hip_propagate_ctrl", self._controller_module, Y, T, ns, xs, us, steps, status)
         return xs, us, steps, status
 
     def _raise_unless_ok(self, status):
@@ -187,11 +194,7 @@ class Integrator(IntegratorOptions):
     def _propagate(self, Y, T, ns):
         m, n = Y.shape[0], self.xv
         xs, steps, status = np.empty((m, ns, n)), np.empty((m, 2), dtype=np.int32), np.empty(m, dtype=np.int32)
-        opt, keep = self._c()
-        _lib.check(_lib.lib().asset_hip_propagate(self._device_name().encode(), Y.ctypes.data_as(_dp), m, T.ctypes.data_as(_dp), int(ns),
-                                                  C.byref(opt), xs.ctypes.data_as(_dp), steps.ctypes.data_as(_ip), status.ctypes.data_as(_ip),
-                                                  self.device), "asset_hip_propagate")
-        del keep
+        self._call("asset_hip_propagate", self._device_name, Y, T, ns, xs, steps, status)
         return xs, steps, status
 
     def _states(self, Y, T, ns):
@@ -261,13 +264,8 @@ class Integrator(IntegratorOptions):
         r = dict(xf=np.empty((m, n)), t_end=np.empty(m), stopped=np.empty(m, dtype=np.int32), ev_count=np.empty((m, ne), dtype=np.int32),
                  ev_rows=np.empty((m, ne, K, n + 1)), ev_resid=np.empty((m, ne, K)), ev_conv=np.empty((m, ne, K), dtype=np.int32),
                  steps=np.empty((m, 2), dtype=np.int32), status=np.empty(m, dtype=np.int32))
-        opt, keep = self._c()
-        p = {k: v.ctypes.data_as(_dp if v.dtype == np.float64 else _ip) for k, v in r.items()}
-        _lib.check(_lib.lib().asset_hip_propagate_events(
-            module.encode(), Y.ctypes.data_as(_dp), m, T.ctypes.data_as(_dp), C.byref(opt), ne, direction.ctypes.data_as(_ip),
-            stop.ctypes.data_as(_ip), float(self.EventTol), int(self.MaxEventIters), K, p["xf"], p["t_end"], p["stopped"], p["ev_count"],
-            p["ev_rows"], p["ev_resid"], p["ev_conv"], p["steps"], p["status"], self.device), "asset_hip_propagate_events")
-        del keep
+        self._call("asset_hip_propagate_events", module, Y, T, None, ne, direction, stop, float(self.EventTol), int(self.MaxEventIters), K,
+                   r["xf"], r["t_end"], r["stopped"], r["ev_count"], r["ev_rows"], r["ev_resid"], r["ev_conv"], r["steps"], r["status"])
         return r
 
     def _propagate_events(self, Y, T, events, details):
@@ -381,19 +379,12 @@ class Integrator(IntegratorOptions):
         m, n, N = Y.shape[0], self.xv, self._width()
         xf, jac = np.empty((m, 1, n)), np.empty((m, n, N + 1))
         steps, status = np.empty((m, 2), dtype=np.int32), np.empty(m, dtype=np.int32)
-        opt, keep = self._c()
         law = self._law()
         uf = np.empty((m, 1, self._uv)) if law else None   # (with a control law: the law at the end row, asset_hip_propagate_ctrl_stm)
-        name = self._controller_module() if law else self._device_name()
-        head = (name.encode(), Y.ctypes.data_as(_dp), m, T.ctypes.data_as(_dp), C.byref(opt), xf.ctypes.data_as(_dp)) \
-            + ((uf.ctypes.data_as(_dp),) if law else ()) + (jac.ctypes.data_as(_dp), steps.ctypes.data_as(_ip), status.ctypes.data_as(_ip))
-        entry = "asset_hip_propagate_ctrl_stm" if law else "asset_hip_propagate_stm"
-        if details:                                       # (the diagnostic variant: also the last lane's end state)
-            last = np.empty((m, n))
-            _lib.check(getattr(_lib.lib(), entry + "_lanes")(*head, last.ctypes.data_as(_dp), self.device), entry + "_lanes")
-        else:
-            _lib.check(getattr(_lib.lib(), entry)(*head, self.device), entry)
-        del keep
+        last = np.empty((m, n)) if details else None       # (the diagnostic variant: also the last lane's end state)
+        out = [a for a in (xf, uf, jac, steps, status, last) if a is not None]
+        entry = ("asset_hip_propagate_ctrl_stm" if law else "asset_hip_propagate_stm") + ("_lanes" if details else "")
+        self._call(entry, self._controller_module if law else self._device_name, Y, T, None, *out)
         if not details:
             self._raise_unless_ok(status)
         rows = self._full_rows(Y, T, xf, uf)[:, 0, :]
