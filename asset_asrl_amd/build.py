@@ -18,7 +18,27 @@ OBJ = os.path.join(CSRC, "obj")
 LIB = os.path.join(HERE, "libasset_hip.so")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = "gfx950"
-FLAGS = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-Wno-unused-value"]
+# Kernel-argument preload: the leading parameters of every kernel arrive in user SGPRs at wave launch instead of being loaded from the
+# kernel-argument segment by the wave's first instructions.  The count is in PARAMETERS -- the hot list of csrc/eval_args.h
+# (ASSET_EVAL_HOT_PARAMS; 14 dwords, all the user SGPRs there are); kernels with other parameter lists get what fits of theirs.  Part of
+# FLAGS, so the run-time compile options (jit.rtc_options) and the module cache key carry it.  A build without it runs the same
+# signatures through loads: flags_without_preload() is what the variant build uses (tools/build_variants.py, -DASSET_KERNARG_PRELOAD=0).
+KERNARG_PRELOAD = ["-mllvm", "-amdgpu-kernarg-preload-count=10"]
+FLAGS = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-Wno-unused-value"] + KERNARG_PRELOAD
+
+
+def flags_without_preload():
+    out, skip = [], False
+    for i, f in enumerate(FLAGS):
+        if skip:
+            skip = False
+        elif f == "-mllvm" and FLAGS[i + 1] == KERNARG_PRELOAD[1]:
+            skip = True
+        else:
+            out.append(f)
+    return out
+
+
 # Scheduler by translation unit.  The segment loops of the resident kernel are single basic blocks bound by LDS / matrix-instruction
 # latency; the scheduler that goes for instruction-level parallelism (instead of the lowest register pressure) hides more of it in
 # the shapes with registers to spare -- measured per unit, all 1 000-step bench lines: Reentry-LGL7 29.9 -> 29.3 us (5 000 segments

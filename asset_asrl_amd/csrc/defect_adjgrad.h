@@ -54,7 +54,8 @@ struct OdeOutG {    // only g (the value of a cardinal node is already in LDS)
 // ADJ = false: the value-only kind (constraints, evalOCC) through the same phases without the gradient parts -- nothing
 // goes through the workspace (the value path of lgl_defect_kernel writes f_j and f^_i to the slots and reads them back).
 template <class Ode, int SCH, bool BLOCKED, bool ADJ = true>
-__global__ __launch_bounds__(64) void lgl_adjgrad_kernel(EvalArgs a) {
+__global__ __launch_bounds__(64) void lgl_adjgrad_kernel(ASSET_EVAL_PARAMS) {
+  ASSET_EVAL_REBUILD
   using D = Dims<Ode, SCH, BLOCKED>;
   using AD = AdjDims<D>;
   constexpr int CS = D::CS, K = D::K, n = D::n, m = D::m, p = D::p, q = D::q, N = D::N, T = D::T, TF = D::TF, P0 = D::P0;

@@ -9,6 +9,7 @@
 #include <cstdint>
 #include <type_traits>
 
+#include "eval_args.h"
 #include "lgl_tables.h"
 
 #define ASSET_ODE_WAVES_PER_SIMD 1    // register budget of the ODE-stage kernel
@@ -28,51 +29,6 @@
 namespace asset_hip {
 
 static __constant__ LglTab d_lgl_tab[4] = ASSET_LGL_TABLE_INIT;
-
-struct EvalArgs {
-  int nseg;
-  const double* X;     // NLP primal vector (device)
-  const double* L;     // equality multipliers (device); unused for value-only
-  const int* vindex;   // [IR x nseg] column-major (device)
-  const int* cindex;   // [OR x nseg] column-major (device)
-  double* FX;          // [nseg x OR] blocks or null
-  double* AGX;         // [nseg x IR] blocks or null
-  double* KKT;         // [nseg x KSTRIDE] blocks (layout: Dims::KL below) or null
-  double* work;        // [grid][G][SLOT] per-workgroup ODE result slots (L2-resident scratch in HBM)
-  // On-device assembly (dense stage, ASM kernels): KKT entries go into the solver's value array instead of being
-  // stored as blocks (DenseFunctionBase.h:1413-1523 KKTFillAll / KKTFillJac; locations NonLinearProgram.cpp:316-330;
-  // the reference serialises clashing columns with mutexes, KKTClashes / KKTLocks).  kmap holds, per segment and in
-  // accumulator-fragment order, one entry per lane and accumulator entry:  m >= 0 -- value location used by this slot
-  // alone: the entry is STORED (the caller hands over zeros there, as the reference zeroes the KKT values before every
-  // evaluation, PSIOPT.cpp:107);  m <= -2 -- location -(m+2) is shared with other slots of this constraint (boundary
-  // nodes of adjacent segments, phase parameters): no-return f64 atomic add;  -1 -- no KKT slot.  In accumulate mode
-  // every slot is encoded as shared, which makes the evaluation a true += at about 1.4e11 atomics/s.
-  const int* kmap = nullptr;
-  double* values = nullptr;
-  // Locations that three or more slots share (entries between phase parameters: one contribution per segment) are not
-  // added to atomically -- the order of the additions, hence the last bits of the sum, would change from run to run --
-  // but STAGED: the map names such a location as nvalues + k, slot k of `stage`, every staged slot owns one cell, and
-  // asm_reduce_kernel sums the cells of each location in slot order afterwards (capi.hip).  Locations with exactly two
-  // contributors (boundary nodes of adjacent segments) keep the atomic: a + b = b + a, bit for bit.
-  double* stage = nullptr;
-  int nvalues = 0;
-  // per-lane constants of the dense stage, computed once per handle (defect_kernels.h: LaneConsts, lane_setup_kernel)
-  const void* lane_consts = nullptr;
-  const void* lane_consts_res = nullptr;   // the record of the resident kernel (defect_resident.h: ResLane)
-  // Index tables whose rows are runs -- vindex[s][k] = aff_v0 + s aff_vs + k, cindex[s][k] = aff_c0 + s aff_cs + k, what a
-  // phase without BlockConstant controls and ODE parameters produces (PhaseIndexer.cpp:361-372, 179-189) -- are recognised
-  // when the handle is created: the resident kernel then forms the addresses of z and lam itself instead of loading them
-  // (one dependent memory round trip less at the start of every wave).
-  int affine = 0, aff_v0 = 0, aff_vs = 0, aff_c0 = 0, aff_cs = 0;
-  // plain functions (func_kernels.h): constants of every application, [nseg][F::NACONST] (vf.ApplConst) or null
-  const double* appl_consts = nullptr;
-  // bit 0 (ASSET_HIP_KEEP_HESSIAN_SLOTS, Jacobian kinds): the Hessian slots of the KKT blocks are not written at all
-  // instead of being written as zeros -- KKTFillJac (DenseFunctionBase.h:1468-1523) never reads them
-  int flags = 0;
-  // Heavy right-hand sides: segments per group of the unit kernels that wrote the workspace slots (0: unknown).  The dense
-  // part behind them then takes every group's segments on the XCD whose L2 holds them (defect_resident.h, GIVEN).
-  int units_gp = 0;
-};
 
 // ---------------------------------------------------------------------------------------------- sizes
 template <class Ode, int CS_, bool BLOCKED_>

@@ -1577,7 +1577,8 @@ __device__ __forceinline__ void lgl_defect_body(const EvalArgs& a) {
 template <class Ode, int SCH, bool BLOCKED, int G, int LEVEL, int STAGE, bool ASM = false>
 __global__ __launch_bounds__(STAGE == 4 ? 128 : 64, STAGE >= 2 ? (Dims<Ode, SCH, BLOCKED>::lds_bytes_dense() * 4 * ASSET_DENSE_WAVES_PER_SIMD <= 160 * 1024
                                                    ? ASSET_DENSE_WAVES_PER_SIMD : 1)   // LDS-bound to one wave per SIMD anyway: take the registers
-                                             : ASSET_ODE_WAVES_PER_SIMD) void lgl_defect_kernel(EvalArgs a) {
+                                             : ASSET_ODE_WAVES_PER_SIMD) void lgl_defect_kernel(ASSET_EVAL_PARAMS) {
+  ASSET_EVAL_REBUILD
   if constexpr (lgl_variant_valid<Dims<Ode, SCH, BLOCKED>, LEVEL, STAGE>()) lgl_defect_body<Ode, SCH, BLOCKED, G, LEVEL, STAGE, ASM>(a);
 }
 

@@ -262,6 +262,45 @@ __device__ __attribute__((noinline, not_tail_called)) void res_cardinal_value(ld
   }
 }
 
+// P1 of a run (index rows that are runs, p == 0) with the node's q inputs as arguments: the CALLER loads them.  A call waits for every
+// scalar load its caller has in flight, and at the head of a launch those are the loads of the kernel-argument segment, which miss
+// every cache -- with the loads of X inside the callee the two round trips to memory were one behind the other.  The address of the
+// run is formed from preloaded arguments alone (eval_args.h), so the caller's loads of X are the wave's first memory instructions and
+// the segment's loads fly beside them.  Same generated body, same arithmetic.  (Arguments travel in VGPRs, 32 at most: RUN_ARGS_OK.)
+template <class D>
+struct RunValsIn {
+  const double* yv;
+  __device__ double y(int i) const { return yv[i]; }
+  __device__ double lam(int) const { return 0.0; }
+  __device__ double saved(int) const { return 0.0; }
+};
+template <class D>
+constexpr bool RUN_ARGS_OK = (D::p == 0 && 2 * D::q + 2 <= 32);
+template <class Ode, class D, int LEVEL, bool WITHJ, class... Y>
+__device__ __attribute__((noinline, not_tail_called)) void res_cardinal_value_args(lds_double* S, int j, Y... y) {
+  using R = ResDims<D>;
+  static_assert(sizeof...(Y) == D::q, "one argument per input of a node");
+  const double yv[D::q] = {y...};
+  OdeOutRes<D> out{S + D::w_Cf + j * D::n, (LEVEL == 1 || WITHJ) ? S + D::w_CJ + j * D::NZJ : nullptr, nullptr, nullptr,
+                   LEVEL == 1 ? nullptr : S + R::s_SV + j * R::SV_LD};
+  RunValsIn<D> in{yv};
+  if constexpr (LEVEL == 1) Ode::fj(in, out); else if constexpr (WITHJ) Ode::fj_save(in, out); else Ode::f_save(in, out);
+}
+template <class T, T... I>
+struct RunIdx {};                                   // 0 .. q-1 as a pack (the compiler's own builtin: no <utility> in a run-time module)
+template <int N>
+using RunIdxTo = __make_integer_seq<RunIdx, int, N>;
+template <class Ode, class D, int LEVEL, bool WITHJ, int... I>
+__device__ __forceinline__ void res_cardinal_value_run(lds_double* S, int j, const double* Xs, RunIdx<int, I...>, long long* t_arrived = nullptr) {
+  const double* const yj = Xs + j * D::q;
+  const double yv[D::q] = {yj[I]...};
+#if defined(ASSET_TIMING)   // (measurement build: the clock when the node's inputs have come back)
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  if (t_arrived) *t_arrived = clock64();
+#endif
+  res_cardinal_value_args<Ode, D, LEVEL, WITHJ>(S, j, yv[I]...);
+}
+
 // P2: interior point i: x^, tau, u^ ; f^, J^, g^ = J^^T lam_i, H^ = lam_i^T d2f
 template <class Ode, class D, int LEVEL = 2, bool RDF = ResDims<D>::ROWDPP>
 __device__ __attribute__((noinline, not_tail_called)) void res_interior(lds_double* S, int i, const LglTab* tabp, bool have_lam,
@@ -685,10 +724,29 @@ __device__ __forceinline__ void lgl_resident_body(const EvalArgs& a) {
   const LglTab& tab = *reinterpret_cast<const LglTab*>((double*)tabL);
   const LglTab& ctab = d_lgl_tab[D::TAB];                           // compile-time indices: scalar loads
 
+#if defined(ASSET_TIMING)
+  long long tstamp[24];
+  int nts = 0;
+#define RTS() do { if (nts < 24) tstamp[nts++] = clock64(); } while (0)
+  long long t_x = 0;                  // when the inputs of this lane's cardinal node have arrived (P1 of a run)
+  RTS();                              // the wave's first instructions
+#define RTSG() do { if (g == 1) RTS(); } while (0)
+#if defined(ASSET_TIMING_FINE)          // (inside the tile columns: products + T writes | LDS hand-over | J^T tile + stores | column role, rank-2 | H stores)
+#define RTSF() do { if (g == 1) RTS(); } while (0)
+#else
+#define RTSF() do {} while (0)
+#endif
+#else
+#define RTS() do {} while (0)
+#define RTSF() do {} while (0)
+#define RTSG() do {} while (0)
+#endif
   // this wave's share of the mesh: contiguous, balanced (same rule as IndexingData.h:117-146), walked in groups of at most GR
   // segments (equal groups: 7 segments are 4 + 3).  One group per wave up to GR segments per wave; on larger meshes the waves
   // drift apart from group to group, so that the ODE stage of some runs under the block stores of the others.
-  const int nshare = int(gridDim.x) * NWV, share = int(blockIdx.x) * NWV + wv;
+  // (the workgroups of the launch are an argument, a.nwg -- the launcher's grid, in a preloaded SGPR: gridDim.x is a load from the
+  //  hidden arguments, a round trip to memory before the wave knows its share)
+  const int nshare = a.nwg * NWV, share = int(blockIdx.x) * NWV + wv;
   const int per = a.nseg / nshare, rem = a.nseg % nshare;
   int wg_first = share * per + min(share, rem), wg_count = per + (share < rem ? 1 : 0);
   // (PAIR) which shares take the `rem` segments of an uneven split: wave 0 of every workgroup first, then wave 1.  A SIMD hosts wave 1
@@ -696,7 +754,7 @@ __device__ __forceinline__ void lgl_resident_body(const EvalArgs& a) {
   // to the SIMDs of the first rem / 2 workgroups: at 5 000 Reentry-LGL7 segments (shares of 3 and 2) the busiest SIMD has 5
   // segments instead of 6.
   auto pair_range = [&](int s, int& first, int& count) {
-    const int b = s >> 1, w = s & 1, nwg = int(gridDim.x);
+    const int b = s >> 1, w = s & 1, nwg = a.nwg;
     const int rem0 = min(rem, nwg), rem1 = max(rem - nwg, 0);      // extras of the waves 0 / of the waves 1, workgroups in order
     first = s * per + min(b, rem0) + min(b, rem1) + ((w == 1 && b < rem0) ? 1 : 0);
     count = per + ((w == 0 ? b < rem0 : b < rem1) ? 1 : 0);
@@ -704,15 +762,19 @@ __device__ __forceinline__ void lgl_resident_body(const EvalArgs& a) {
   // (measured, Reentry-LGL7: 3 000 segments 18.8 -> 18.2 us, 5 000: 23.5 -> 22.8, 7 000: 27.6 -> 26.7, 9 000: 31.7 -> 30.7; with more
   //  extras than workgroups -- 10 000: 1 808 for 1 024 -- the busiest SIMD has two long shares either way and the plain rule is
   //  0.15 us faster)
-  const bool w0first = rem <= int(gridDim.x);
+  const bool w0first = rem <= a.nwg;
   if constexpr (PAIR) { if (w0first) pair_range(share, wg_first, wg_count); }
+#if defined(ASSET_TIMING)
+  asm volatile("" ::"s"(wg_first), "s"(wg_count));   // the share is formed from nseg and the workgroup count: the arguments are there
+  RTS();
+#endif
   if constexpr (GIVEN) {
     // Behind the one-launch unit stage (registry.h): group g of units_gp segments was evaluated on XCD g % 8, and this workgroup runs
     // on XCD blockIdx % 8 -- it takes its segments from that XCD's groups (every group split evenly among the waves the XCD has
     // for it), so the slots come out of the L2 they were written into instead of from memory: the copy of a Betts-LGL5 slot was
     // 4-5 us of the dense part's 13.
-    if (a.units_gp > 0 && (int(gridDim.x) & 7) == 0) {
-      const int gp = a.units_gp, x = int(blockIdx.x) & 7, k = int(blockIdx.x) >> 3, nW = int(gridDim.x) >> 3;
+    if (a.units_gp > 0 && (a.nwg & 7) == 0) {
+      const int gp = a.units_gp, x = int(blockIdx.x) & 7, k = int(blockIdx.x) >> 3, nW = a.nwg >> 3;
       const int G = (a.nseg + gp - 1) / gp, Gx = x < G ? (G - x + 7) >> 3 : 0;     // groups of this XCD: x, x + 8, ...
       const int wpg = Gx > 0 ? nW / Gx : 0, gi = wpg > 0 ? k / wpg : 0, wi = wpg > 0 ? k - gi * wpg : 0;
       wg_first = 0, wg_count = 0;
@@ -748,25 +810,10 @@ __device__ __forceinline__ void lgl_resident_body(const EvalArgs& a) {
   //  changes nothing: 35.1-35.2 us each)
   // the second wave of its SIMD (workgroups are dealt breadth first: b and b + gridDim/2 share a SIMD; in the pair form b's wave 1
   // and (b + gridDim/4)'s wave 0 do)
-  const bool young = PAIR ? (((4 * int(blockIdx.x)) / max(int(gridDim.x), 1)) & 1) != 0
-                                                    : 2 * int(blockIdx.x) >= int(gridDim.x);
+  const bool young = PAIR ? (((4 * int(blockIdx.x)) / max(a.nwg, 1)) & 1) != 0
+                                                    : 2 * int(blockIdx.x) >= a.nwg;
   lds_double* const region0 = (lds_double*)lds;                     // (PAIR) wave 0's region; wave 1's follows
 
-#if defined(ASSET_TIMING)
-  long long tstamp[24];
-  int nts = 0;
-#define RTS() do { if (nts < 24) tstamp[nts++] = clock64(); } while (0)
-#define RTSG() do { if (g == 1) RTS(); } while (0)
-#if defined(ASSET_TIMING_FINE)          // (inside the tile columns: products + T writes | LDS hand-over | J^T tile + stores | column role, rank-2 | H stores)
-#define RTSF() do { if (g == 1) RTS(); } while (0)
-#else
-#define RTSF() do {} while (0)
-#endif
-#else
-#define RTS() do {} while (0)
-#define RTSF() do {} while (0)
-#define RTSG() do {} while (0)
-#endif
 #if defined(ASSET_WALLCLOCK)
   const long long wall_t0 = wall_clock64();
 #endif
@@ -886,15 +933,17 @@ __device__ __forceinline__ void lgl_resident_body(const EvalArgs& a) {
         ci[t] = (e < gall * OR) ? a.cindex[size_t(pseg(g)) * OR + r] : -1;
       }
     }
-    double tabv[NTAB];
-#pragma unroll
-    for (int t = 0; t < NTAB; t++)
-      tabv[t] = (lane + 64 * t < D::TABSZ) ? reinterpret_cast<const double*>(&d_lgl_tab[D::TAB])[lane + 64 * t] : 0.0;
+    // (the values before the tables: with the tables' loads issued first, the wait for the index loads of the other branch was a
+    //  wait for a table load in the run case too -- a round trip to memory before the first load of X left the wave)
     double zv[NZ], lv[NL];
 #pragma unroll
     for (int t = 0; t < NZ; t++) zv[t] = (vi[t] >= 0) ? a.X[vi[t]] : 0.0;
 #pragma unroll
     for (int t = 0; t < NL; t++) lv[t] = (ci[t] >= 0 && a.L) ? a.L[ci[t]] : 0.0;
+    double tabv[NTAB];
+#pragma unroll
+    for (int t = 0; t < NTAB; t++)
+      tabv[t] = (lane + 64 * t < D::TABSZ) ? reinterpret_cast<const double*>(&d_lgl_tab[D::TAB])[lane + 64 * t] : 0.0;
 #pragma unroll
     for (int w = 0; w < NWV; w++) {      // every region of the workgroup: tables, constant rows, zero cells
       lds_double* const tb = PAIR ? region0 + w * R::REGION : tabL;
@@ -937,9 +986,19 @@ __device__ __forceinline__ void lgl_resident_body(const EvalArgs& a) {
   } else {
   if (roleA && pj < CS && pg < gall) { // P1 (reads X itself, writes f_j and the saved values: nothing of P0's)
     const int g = pg, j = pj;
-    if (a.affine && D::p == 0) res_cardinal_value<Ode, D, LEVEL, EARLYC>(pslot(g), j, a.X + (a.aff_v0 + pseg(g) * a.aff_vs), nullptr);
-    else res_cardinal_value<Ode, D, LEVEL, EARLYC>(pslot(g), j, a.X, a.vindex + size_t(pseg(g)) * IR);
+    if (a.affine && D::p == 0) {
+      const double* const Xs = a.X + (a.aff_v0 + pseg(g) * a.aff_vs);
+#if defined(ASSET_TIMING)
+      if constexpr (RUN_ARGS_OK<D>) res_cardinal_value_run<Ode, D, LEVEL, EARLYC>(pslot(g), j, Xs, RunIdxTo<D::q>{}, &t_x);
+#else
+      if constexpr (RUN_ARGS_OK<D>) res_cardinal_value_run<Ode, D, LEVEL, EARLYC>(pslot(g), j, Xs, RunIdxTo<D::q>{});
+#endif
+      else res_cardinal_value<Ode, D, LEVEL, EARLYC>(pslot(g), j, Xs, nullptr);
+    } else res_cardinal_value<Ode, D, LEVEL, EARLYC>(pslot(g), j, a.X, a.vindex + size_t(pseg(g)) * IR);
   }
+#if defined(ASSET_TIMING)
+  if (grp == 0 && roleA && PAIR && nts < 24) tstamp[nts++] = t_x != 0 ? t_x : clock64();   // (wave 0: X there, then P1 done below)
+#endif
   pair_sync();
   RTS();
   // (Round 5 also ran the interior phase and the cardinal second-derivative phase in HALVES -- both waves of a pair, each one half of
@@ -1476,6 +1535,8 @@ __device__ __forceinline__ void lgl_resident_body(const EvalArgs& a) {
 #if defined(ASSET_TIMING)
   if (blockIdx.x == 7 && wv == 0 && lane0 == 0 && a.FX)
     for (int t = 0; t + 1 < nts; t++) a.FX[size_t(wg_first) * OR + t] = double(tstamp[t + 1] - tstamp[t]);
+  if (PAIR && blockIdx.x == 7 && wv == 1 && lane0 == 0 && a.AGX)      // (wave 1's stamps -- its gather is the third delta -- go to AGX)
+    for (int t = 0; t + 1 < nts; t++) a.AGX[size_t(wg_first) * IR + t] = double(tstamp[t + 1] - tstamp[t]);
 #endif
 #if defined(ASSET_WALLCLOCK)   // (tuning builds) 100 MHz wall-clock at the start and the end of every wave, left in FX
   if (lane0 == 0 && a.FX && wg_count > 0) {
@@ -1492,7 +1553,8 @@ __device__ __forceinline__ void lgl_resident_body(const EvalArgs& a) {
 // FORM 1: the row-wise dense part for a shape whose default form is tiles (ResDims::RD_ALT; one-group kernel, level 2, blocks)
 template <class Ode, int SCH, bool BLOCKED, int LEVEL = 2, bool ASM = false, bool LOOP = false, bool GIVEN = false, bool LPAIR = false, int FORM = -1>
 __global__ __launch_bounds__((!GIVEN && ResDims<Dims<Ode, SCH, BLOCKED>>::PAIR && (!LOOP || LPAIR)) ? 128 : 64, (ResDims<Dims<Ode, SCH, BLOCKED>>::WPS))
-void lgl_resident_kernel(EvalArgs a) {
+void lgl_resident_kernel(ASSET_EVAL_PARAMS) {
+  ASSET_EVAL_REBUILD
 #if defined(ASSET_EXP_NULL)   // (experiment: the cost of the launch itself)
   if (a.nseg > 0) return;
 #endif

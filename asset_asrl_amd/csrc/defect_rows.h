@@ -589,7 +589,8 @@ __device__ __forceinline__ void lgl_rows_body(const EvalArgs& a, const double* _
 }
 
 template <class Ode, int SCH, bool BLOCKED, int LEVEL = 2>
-__global__ __launch_bounds__(256, 1) void lgl_rows_kernel(EvalArgs a, const double* __restrict__ work_ro) {
+__global__ __launch_bounds__(256, 1) void lgl_rows_kernel(ASSET_EVAL_PARAMS, const double* __restrict__ work_ro) {
+  ASSET_EVAL_REBUILD
   if constexpr (RowsDims<Dims<Ode, SCH, BLOCKED>>::OK) lgl_rows_body<Ode, SCH, BLOCKED, LEVEL>(a, work_ro);
 }
 

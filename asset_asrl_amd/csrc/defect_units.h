@@ -320,7 +320,8 @@ __device__ __forceinline__ void lgl_ode_units_body(const EvalArgs& a, int gp) {
 // The kernel proper (ODEs whose generated functor is cut into units; an empty kernel for the others, which a run-time
 // compiled module still names).
 template <class Ode, int SCH, bool BLOCKED, int PHASE>
-__global__ __launch_bounds__(64, 1) void lgl_ode_units_kernel(EvalArgs a, int gp) {
+__global__ __launch_bounds__(64, 1) void lgl_ode_units_kernel(ASSET_EVAL_PARAMS, int gp) {
+  ASSET_EVAL_REBUILD
   if constexpr (Ode::NUNITS > 1) lgl_ode_units_body<Ode, SCH, BLOCKED, PHASE>(a, gp);
 }
 

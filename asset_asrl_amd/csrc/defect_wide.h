@@ -599,7 +599,8 @@ __device__ __forceinline__ void lgl_wide_dense_body(const EvalArgs& a) {
 // The kernel proper (wide shapes only; an empty kernel for the others, which a run-time compiled module still names).
 template <class Ode, int SCH, bool BLOCKED, int LEVEL, bool ASM>
 __global__ __launch_bounds__(256, (Dims<Ode, SCH, BLOCKED>::lds_bytes_dense() * ASSET_WIDE_WGS <= 160 * 1024 ? ASSET_WIDE_WGS : 1))
-void lgl_wide_dense_kernel(EvalArgs a) {
+void lgl_wide_dense_kernel(ASSET_EVAL_PARAMS) {
+  ASSET_EVAL_REBUILD
   if constexpr (Dims<Ode, SCH, BLOCKED>::WIDE && LEVEL >= 1) lgl_wide_dense_body<Ode, SCH, BLOCKED, LEVEL, ASM>(a);
 }
 

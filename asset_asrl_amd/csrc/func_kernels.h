@@ -187,7 +187,8 @@ __device__ __forceinline__ void func_body(const EvalArgs& a, int block) {   // b
 }
 
 template <class F, int LEVEL, bool ASM>
-__global__ __launch_bounds__(64, ASSET_FUNC_WAVES) void func_kernel(EvalArgs a) {
+__global__ __launch_bounds__(64, ASSET_FUNC_WAVES) void func_kernel(ASSET_EVAL_PARAMS) {
+  ASSET_EVAL_REBUILD
   func_body<F, LEVEL, ASM>(a, int(blockIdx.x));
 }
 

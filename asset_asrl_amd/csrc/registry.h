@@ -477,6 +477,16 @@ inline hipError_t plan_lgl(const KernelTable& t, const PlanRequest& rq, int nseg
   return hipSuccess;
 }
 
+// Every kernel that takes the arguments of an evaluation has the one parameter list of eval_args.h, and this is the one place that
+// fills it: the values through eval_args_pack -- with the workgroups the launch is made with -- then the kernel's own trailing parameter.
+inline hipError_t launch_eval(const KRef& k, dim3 grid, dim3 block, size_t shmem, hipStream_t st, const EvalArgs& a, void* extra = nullptr) {
+  EvalKernArgs ka;
+  void* kargs[kEvalParams + 1];
+  eval_args_pack(a, grid.x, ka, kargs);
+  kargs[kEvalParams] = extra;      // (kernels without a trailing parameter never read it)
+  return klaunch(k, grid, block, shmem, st, kargs);
+}
+
 inline hipError_t launch_plan(const KernelTable& t, const LaunchPlan& p, const EvalArgs& a, hipStream_t st) {
   EvalArgs args = a;
   for (int i = 0; i < p.nsteps; i++) {
@@ -484,8 +494,8 @@ inline hipError_t launch_plan(const KernelTable& t, const LaunchPlan& p, const E
     if (i + 1 == p.nsteps && p.units_gp > 0) args.units_gp = p.units_gp;
     int gp = s.gp;
     const double* work_ro = a.work;
-    void* kargs[] = {&args, s.extra == PLAN_GP ? static_cast<void*>(&gp) : static_cast<void*>(&work_ro)};   // (one-argument kernels read the first only)
-    const hipError_t e = klaunch(t.k[s.slot], dim3(s.grid_x, s.grid_y), dim3(s.block), s.lds_bytes, st, kargs);
+    void* const extra = s.extra == PLAN_GP ? static_cast<void*>(&gp) : static_cast<void*>(&work_ro);
+    const hipError_t e = launch_eval(t.k[s.slot], dim3(s.grid_x, s.grid_y), dim3(s.block), s.lds_bytes, st, args, extra);
     if (e != hipSuccess) return e;
   }
   return hipSuccess;
@@ -513,10 +523,8 @@ inline FuncPlan plan_func(const long long* meta, int level, bool assembled, int 
 }
 inline hipError_t launch_func_table(const KernelTable& t, int level, const EvalArgs& a, hipStream_t st) {
   if (level < 0 || level > 2) return hipErrorInvalidValue;
-  EvalArgs args = a;
-  void* kargs[] = {&args};
   const FuncPlan p = plan_func(t.meta, level, a.kmap != nullptr, a.nseg);
-  return klaunch(t.k[p.slot], dim3(p.grid), dim3(64), p.lds_bytes, st, kargs);
+  return launch_eval(t.k[p.slot], dim3(p.grid), dim3(64), p.lds_bytes, st, a);
 }
 
 inline hipError_t entry_launch(const KernelEntry* ke, int level, const EvalArgs& a, int cus, hipStream_t st) {

@@ -20,7 +20,8 @@ VARIANTS = {
     "earlyc0_twobody": ("tu_twobody_lt_lgl3_1", ["-DASSET_RES_EARLYC=0"], ("twobody_lt", "LGL5", 1), "C passes behind the cardinal second-derivative phase"),
     "unitc0_reentry": ("tu_reentry_lgl4_0", ["-DASSET_RD_UNITC=0"], ("reentry", "LGL7", 0), "the general C pass (J rows and the gradient row through one path) on a two-form shape"),
     "unitc0_twobody": ("tu_twobody_lt_lgl3_1", ["-DASSET_RD_UNITC=0"], ("twobody_lt", "LGL5", 1), "the general C pass on a shape with segment parameters"),
-    "looppair0_reentry": ("tu_reentry_lgl3_1", ["-DASSET_RES_LOOP_PAIR=0"], ("reentry", "LGL5", 1), "looped block kernel as single waves on a shape that is built with the pair form"),
+    "preload0_reentry": ("tu_reentry_lgl4_0", ["-DASSET_KERNARG_PRELOAD=0"], ("reentry", "LGL7", 0), "kernel arguments loaded from their segment, no preload into SGPRs (tools/build_one.py drops the compiler option)"),
+    "looppair0_reentry":("tu_reentry_lgl3_1", ["-DASSET_RES_LOOP_PAIR=0"], ("reentry", "LGL5", 1), "looped block kernel as single waves on a shape that is built with the pair form"),
 }
 
 
