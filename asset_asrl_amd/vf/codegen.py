@@ -28,7 +28,7 @@ from typing import Dict, List, Sequence, Tuple
 from .functions import VectorFunction
 import numpy as np
 
-from .ir import COND_OPS, TABLES
+from .ir import COND_OPS, TABLES, tab_array
 from .ir import GRAPH as G
 from .ir import Node, topo_order
 
@@ -593,7 +593,7 @@ class _Printer:
             return f"{self.tabprefix or 'asset_'}tab_find({self.tabprefix}TAB_{n.value}_t, {tab.tsize}, {a[0]})"
         if op == "tabget":
             dg, arr, row, off = n.value
-            return f"{self.tabprefix}TAB_{dg}_{arr}[{row * TABLES[dg].tsize + off} + (int){a[0]}]"
+            return f"{self.tabprefix}TAB_{dg}_{arr}[{row * tab_array(TABLES[dg], arr)[1] + off} + (int){a[0]}]"
         if op == "abs":
             return f"fabs({a[0]})"
         if op == "sign":
@@ -613,10 +613,17 @@ def table_arrays(roots: Sequence[Node]) -> List[Tuple[str, List[float]]]:
             need.add((n.value, "t"))
     out = []
     for dg, arr in sorted(need):
-        tab = TABLES[dg]
-        data = tab.ts if arr == "t" else (tab.vs if arr == "v" else tab.dvs_dts)
-        out.append((f"TAB_{dg}_{arr}", [float(v) for v in np.asarray(data, dtype=float).ravel()]))
+        out.append((f"TAB_{dg}_{arr}", [float(v) for v in np.asarray(tab_array(TABLES[dg], arr)[0], dtype=float).ravel()]))
+    total = sum(len(v) for _, v in out)
+    if total > TABLE_ENTRY_CAP:
+        raise ValueError(f"the expression embeds {total} numbers of tabulated data in one module; the cap is {TABLE_ENTRY_CAP} "
+                         "(vf.codegen.TABLE_ENTRY_CAP: tables are source literals of the module, and its compile time grows with them) -- "
+                         "coarsen or crop the tables, or make them linear")
     return out
+
+
+# Numbers of tabulated data one module may embed (chosen from the measured compile times of large tables)
+TABLE_ENTRY_CAP = 1 << 18
 
 
 # the two look-ups as plain C (the device has them in csrc/asset_math.h)

@@ -688,3 +688,401 @@ class InterpTable1D:
 
     def vf(self) -> "VectorFunction":
         return self(Arguments(1))
+
+
+# --------------------------------------------------------------------------- tables over two and three axes
+
+TABLE_LAYOUT = "record"
+"""How a cubic table over several axes lies in its constant array (DESIGN.md section 5).  "record": the 4 (2-D) or 8 (3-D) quantities
+of one grid node side by side, so the quantities of a corner are one contiguous run of 32 / 64 bytes; "planes": one plane of the
+whole grid per quantity, so a corner is 4 / 8 loads a grid apart.  Read when a table is called as an expression; the two forms are
+different arrays (``TAB_<digest>_r`` / ``TAB_<digest>_p``) and different generated bodies, hence different modules."""
+
+
+def _five_point_weights(ts: np.ndarray, i: int):
+    """(start, w): ``sum_k w[k] v[start + k]`` is dv/dt at ``ts[i]``, exact for quartics -- centred inside, one-sided at the two
+    abscissae on either end (the stencils of InterpTable2D.h:121-198 / InterpTable3D.h:171-218).  The reference solves the 5 x 5 moment
+    system for the weights; they are the derivatives of the five Lagrange polynomials at ``ts[i]``, written out here as products and
+    quotients of differences of the abscissae: the same numbers, each a handful of roundings from exact."""
+    n = ts.size
+    if 2 <= i <= n - 3:
+        start = i - 2
+    elif i < n - 1 - i:
+        start = 0
+    else:
+        start = n - 5
+    x, j = ts[start:start + 5], i - start
+    w = np.zeros(5)
+    for k in range(5):
+        if k == j:
+            for m in range(5):
+                if m != j:
+                    w[k] += 1.0 / (x[j] - x[m])
+            continue
+        num, den = 1.0, 1.0
+        for m in range(5):
+            if m != k:
+                den *= x[k] - x[m]
+                if m != j:
+                    num *= x[j] - x[m]
+        w[k] = num / den
+    return start, w
+
+
+class _TableAxis:
+    """One axis of a table over several: what the look-up nodes need of it (vf/ir.py: ``tabloc``, and ``tabget`` of its array 't')."""
+
+    def __init__(self, ts, letter: str):
+        self.ts = np.asarray(ts, dtype=float).ravel().copy()
+        self.letter = letter
+        self.tsize = int(self.ts.size)
+
+    def finish(self):
+        self.ttotal = float(self.ts[-1] - self.ts[0])
+        even = np.linspace(self.ts[0], self.ts[-1], self.tsize)
+        self.teven = bool(np.max(np.abs(self.ts - even)) <= builtins_abs(self.ttotal) * 1.0e-12)
+        import hashlib
+        self.digest = hashlib.blake2b(b"axis" + self.ts.tobytes(), digest_size=8).hexdigest()
+        from .ir import TABLES
+        TABLES[self.digest] = self
+
+    def locate(self, t: float) -> int:
+        if self.teven:
+            e = int((t - self.ts[0]) / (self.ts[1] - self.ts[0]))
+        else:
+            e = int(np.searchsorted(self.ts, t, side="right")) - 1
+        return max(min(e, self.tsize - 2), 0)
+
+    def outside(self, t: float) -> bool:
+        eps = np.finfo(float).eps * self.ttotal
+        return bool(t < self.ts[0] - eps or t > self.ts[-1] + eps)
+
+    def diff(self, A: np.ndarray, axis: int) -> np.ndarray:
+        """dA/dt along `axis` at every abscissa (five-point stencils)."""
+        A = np.moveaxis(A, axis, 0)
+        out = np.empty_like(A)
+        for i in range(self.tsize):
+            start, w = _five_point_weights(self.ts, i)
+            acc = w[0] * A[start]
+            for k in range(1, 5):
+                acc = acc + w[k] * A[start + k]
+            out[i] = acc
+        return np.moveaxis(out, 0, axis)
+
+
+class _InterpTableND:
+    """What ``InterpTable2D`` and ``InterpTable3D`` share.  Axes and quantities are numbered in ARGUMENT order (x, y[, z]); quantity
+    ``q`` of a cubic table is the derivative of the data along every axis whose bit is set in ``q`` (2-D: z, z_x, z_y, z_xy; 3-D: f,
+    f_x, f_y, f_xy, f_z, f_xz, f_yz, f_xyz).  ``self._Q[q]`` has the shape of the data as the user passed it, ``self._strides[a]`` is
+    the distance, in grid nodes, of two neighbours along axis a.
+
+    The interpolant of a cell is the tensor-product cubic Hermite polynomial that matches every quantity at every corner.  It is
+    evaluated NESTED: a 1-D Hermite interpolation along x for each quantity without x and each corner without x, then along y, then
+    along z (5 interpolations in 2-D, 21 in 3-D) -- the polynomial the reference writes as ``L Z R`` (InterpTable2D.h:238-282) and as
+    64 coefficients (InterpTable3D.h:269-384)."""
+
+    _DIM = 0
+    _NAME = ""
+
+    # ---- the constructor's checks and the arrays
+    def _setup(self, axes, data, kind, data_axis):
+        """axes: _TableAxis in argument order; data_axis[a]: the axis of `data` that runs along axes[a]."""
+        if kind in ("cubic", "Cubic"):
+            self.kind = "cubic"
+        elif kind in ("linear", "Linear"):
+            self.kind = "linear"
+        else:
+            raise ValueError("Unrecognized interpolation type")
+        self._axes, self._data_axis = axes, data_axis
+        self._data = np.array(data, dtype=float)
+        self._check_sizes()
+        for ax in axes:
+            ax.finish()
+        self.WarnOutOfBounds, self.ThrowOutOfBounds = True, False
+        d = self._DIM
+        self._nq = (1 << d) if self.kind == "cubic" else 1
+        self._Q = self._derivs() if self.kind == "cubic" else [self._data]
+        nodes = int(self._data.size)
+        st = [int(s) // self._data.itemsize for s in np.ascontiguousarray(self._data).strides]
+        self._strides = [st[data_axis[a]] for a in range(d)]
+        rec = np.stack([np.ascontiguousarray(q).ravel() for q in self._Q], axis=1)        # [node, quantity]
+        # (digest, array name) -> (numbers, row length): vf/ir.py reads the tables' arrays through this
+        self.arrays = {"r": (rec.ravel().copy(), 0), "p": (rec.T.ravel().copy(), 0)}
+        self.entries = nodes * self._nq
+        import hashlib
+        h = hashlib.blake2b(digest_size=8)
+        for part in [self._NAME.encode(), self.kind.encode()] + [ax.ts.tobytes() for ax in axes] \
+                + [np.ascontiguousarray(self._data).tobytes(), str(self._data.shape).encode()]:
+            h.update(part)
+        self.digest = h.hexdigest()
+        from .ir import TABLES
+        TABLES[self.digest] = self
+
+    def _ascending(self, ax, msg):
+        if np.any(np.diff(ax.ts) < 0):
+            raise ValueError(msg)
+
+    # ---- element look-up and the bounds
+    def _elems(self, p):
+        return [ax.locate(float(v)) for ax, v in zip(self._axes, p)]
+
+    def _check_bounds(self, p):
+        if self.WarnOutOfBounds or self.ThrowOutOfBounds:
+            for ax, v in zip(self._axes, p):
+                if ax.outside(v):
+                    msg = f"WARNING: {ax.letter} coordinate falls outside of {self._NAME} range. Data is being extrapolated!!"
+                    if self.ThrowOutOfBounds:
+                        raise ValueError(msg)
+                    import warnings
+                    warnings.warn(msg)
+
+    # ---- the interpolant, numbers
+    @staticmethod
+    def _basis(kind, x, step, order):
+        """Weights of (v0, v1, d0, d1) -- of (v0, v1) for a linear table -- in the `order`-th derivative of the 1-D interpolant."""
+        if kind == "linear":
+            return ((1 - x, x), (-1 / step, 1 / step), (0.0, 0.0))[order]
+        x2, x3 = x * x, x * x * x
+        if order == 0:
+            return (2 * x3 - 3 * x2 + 1, -2 * x3 + 3 * x2, (x3 - 2 * x2 + x) * step, (x3 - x2) * step)
+        if order == 1:
+            return ((6 * x2 - 6 * x) / step, (-6 * x2 + 6 * x) / step, 3 * x2 - 4 * x + 1, 3 * x2 - 2 * x)
+        return ((12 * x - 6) / step ** 2, (-12 * x + 6) / step ** 2, (6 * x - 4) / step, (6 * x - 2) / step)
+
+    def _nest(self, V, weights):
+        """V[q][corner] -> the interpolated number; weights[a]: the 1-D weights along axis a.  Axis by axis, x first."""
+        d, cubic = self._DIM, self.kind == "cubic"
+        for a in range(d):
+            w, rest = weights[a], d - a - 1
+            nV = {}
+            for q in range(1 << rest) if cubic else (0,):
+                for c in range(1 << rest):
+                    lo, hi = V[(q << 1) if cubic else 0][c << 1], V[(q << 1) if cubic else 0][(c << 1) | 1]
+                    if cubic:
+                        dlo, dhi = V[(q << 1) | 1][c << 1], V[(q << 1) | 1][(c << 1) | 1]
+                        nV.setdefault(q, {})[c] = lo * w[0] + hi * w[1] + dlo * w[2] + dhi * w[3]
+                    else:
+                        nV.setdefault(0, {})[c] = lo * w[0] + hi * w[1]
+            V = nV
+        return V[0][0]
+
+    def _cell(self, elems):
+        """V[q][corner]: quantity q at the corner whose bit a says 'the far side along axis a'."""
+        d = self._DIM
+        V = {}
+        for q in range(self._nq):
+            Q = self._Q[q]
+            V[q] = {}
+            for c in range(1 << d):
+                idx = [0] * d
+                for a in range(d):
+                    idx[self._data_axis[a]] = elems[a] + ((c >> a) & 1)
+                V[q][c] = float(Q[tuple(idx)])
+        return V
+
+    def _interp(self, p, deriv: int):
+        p = [float(v) for v in p]
+        self._check_bounds(p)
+        d = self._DIM
+        elems = self._elems(p)
+        V = self._cell(elems)
+        xs, steps = [], []
+        for ax, e, v in zip(self._axes, elems, p):
+            step = ax.ts[e + 1] - ax.ts[e]
+            steps.append(step)
+            xs.append((v - ax.ts[e]) / step)
+
+        def at(orders):
+            return self._nest(V, [self._basis(self.kind, xs[a], steps[a], orders[a]) for a in range(d)])
+
+        out = [at([0] * d)]
+        if deriv > 0:
+            out.append(np.array([at([int(a == i) for a in range(d)]) for i in range(d)]))
+        if deriv > 1:
+            H = np.zeros((d, d))
+            for i in range(d):
+                for j in range(i + 1):
+                    if i == j and self.kind == "linear":
+                        continue                    # (a multilinear cell: the cross terms only)
+                    H[i, j] = H[j, i] = at([int(a == i) + int(a == j) for a in range(d)])
+            out.append(H)
+        return out
+
+    def interp(self, *p):
+        if len(p) != self._DIM:
+            raise ValueError(f"{self._NAME}.interp takes {self._DIM} arguments")
+        if all(np.ndim(v) == 0 for v in p):
+            return self._interp(p, 0)[0]
+        arrs = np.broadcast_arrays(*[np.asarray(v, dtype=float) for v in p])
+        out = np.empty(arrs[0].shape)
+        for idx in np.ndindex(*arrs[0].shape):
+            out[idx] = self._interp([a[idx] for a in arrs], 0)[0]
+        return out
+
+    def interp_deriv1(self, *p):
+        return tuple(self._interp(p, 1))
+
+    def interp_deriv2(self, *p):
+        return tuple(self._interp(p, 2))
+
+    # ---- as an expression
+    def _nodes(self, args: Sequence[Node]) -> Node:
+        d, cubic, dg = self._DIM, self.kind == "cubic", self.digest
+        planes = cubic and TABLE_LAYOUT == "planes"
+        if TABLE_LAYOUT not in ("record", "planes"):
+            raise ValueError(f"TABLE_LAYOUT is 'record' or 'planes', not {TABLE_LAYOUT!r}")
+        c = G.const
+        nq, nodes = self._nq, self.entries // self._nq
+        locs, weights = [], []
+        for ax, t in zip(self._axes, args):
+            loc = G.tabloc(ax.digest, t)
+            t0 = G.tabget(ax.digest, "t", 0, 0, loc)
+            step = c(ax.ts[1] - ax.ts[0]) if ax.teven else G.sub(G.tabget(ax.digest, "t", 0, 1, loc), t0)
+            x = G.div(G.sub(t, t0), step)
+            if cubic:
+                x2 = G.mul(x, x)
+                x3 = G.mul(x2, x)
+                weights.append((G.add(G.sub(G.mul(c(2.0), x3), G.mul(c(3.0), x2)), G.one), G.sub(G.mul(c(3.0), x2), G.mul(c(2.0), x3)),
+                                G.mul(G.add(G.sub(x3, G.mul(c(2.0), x2)), x), step), G.mul(G.sub(x3, x2), step)))
+            else:
+                weights.append((G.sub(G.one, x), x))
+            locs.append(loc)
+        # the cell's first entry: a sum of multiples of piecewise-constant nodes, piecewise constant itself
+        scale = 1 if planes else nq
+        base = G.sum(G.mul(c(float(scale * self._strides[a])), locs[a]) for a in range(d))
+        V = {}
+        for q in range(nq):
+            V[q] = {}
+            for cn in range(1 << d):
+                shift = int(np.dot(self._strides, [(cn >> a) & 1 for a in range(d)]))
+                off = q * nodes + shift if planes else nq * shift + q
+                V[q][cn] = G.tabget(dg, "p" if planes else "r", 0, off, base)
+        for a in range(d):
+            w, rest = weights[a], d - a - 1
+            nV = {}
+            for q in range(1 << rest) if cubic else (0,):
+                for cn in range(1 << rest):
+                    qq = (q << 1) if cubic else 0
+                    terms = [G.mul(V[qq][cn << 1], w[0]), G.mul(V[qq][(cn << 1) | 1], w[1])]
+                    if cubic:
+                        terms += [G.mul(V[qq | 1][cn << 1], w[2]), G.mul(V[qq | 1][(cn << 1) | 1], w[3])]
+                    nV.setdefault(q, {})[cn] = G.sum(terms)
+            V = nV
+        return V[0][0]
+
+    def __call__(self, *args):
+        d = self._DIM
+        if any(isinstance(a, VectorFunction) for a in args):
+            if len(args) == 1:
+                if args[0].ORows() != d:
+                    raise ValueError(f"{self._NAME}: the argument is a function with {d} outputs")
+                return VectorFunction(args[0]._irows, [self._nodes(list(args[0].outs))])
+            if len(args) != d or not all(isinstance(a, VectorFunction) and a.ORows() == 1 for a in args):
+                raise ValueError(f"{self._NAME}: the arguments are {d} scalar functions")
+            if any(a._irows != args[0]._irows for a in args):
+                raise ValueError(f"{self._NAME}: the arguments are functions of one common input size")
+            return VectorFunction(args[0]._irows, [self._nodes([a.outs[0] for a in args])])
+        return self.interp(*args)
+
+    def sf(self) -> "VectorFunction":
+        return self(Arguments(self._DIM))
+
+    def vf(self) -> "VectorFunction":
+        return self(Arguments(self._DIM))
+
+
+class InterpTable2D(_InterpTableND):
+    """Tabulated data ``z(x, y)`` on a rectangular grid, bicubic (Hermite; nodal derivatives from five-point differences) or
+    bilinear -- the reference's ``InterpTable2D`` and ``InterpFunction2D`` (CommonFunctions/InterpTable2D.h).  ``Zs[iy, ix]``: rows
+    run along ``Ys``, columns along ``Xs``.  On the host: ``interp``, ``interp_deriv1`` (value, gradient), ``interp_deriv2`` (value,
+    gradient, Hessian), ``find_elem``; arguments outside the data extrapolate from the end cell (``WarnOutOfBounds`` /
+    ``ThrowOutOfBounds`` as ``InterpTable1D``).
+
+    In an expression -- ``tab(xf, yf)``, ``tab(xy)``, ``tab.sf()``, ``tab.vf()`` -- the table is what ``InterpTable1D`` is: constant
+    arrays of the compiled module, one piecewise-constant look-up node per axis, and the interpolant as an ordinary expression on
+    top, differentiated by the symbolic rules.  Tables are SOURCE LITERALS of the module, so one module embeds at most
+    ``vf.codegen.TABLE_ENTRY_CAP`` numbers of table data (a cubic 2-D table holds 4 per grid node, a cubic 3-D table 8, linear ones 1,
+    plus the abscissae of unevenly spaced axes); code generation raises ``ValueError`` beyond it.  The host interpolation is not
+    capped."""
+
+    _DIM, _NAME = 2, "InterpTable2D"
+
+    def __init__(self, Xs, Ys, Zs, kind="cubic"):
+        self._setup([_TableAxis(Xs, "x"), _TableAxis(Ys, "y")], Zs, kind, data_axis=(1, 0))
+        self.xs, self.ys, self.zs = self._axes[0].ts, self._axes[1].ts, self._data
+        self.xeven, self.yeven = self._axes[0].teven, self._axes[1].teven
+        if self.kind == "cubic":
+            _, self.dzxs, self.dzys, self.dzys_dxs = self._Q
+
+    def _check_sizes(self):
+        ax, ay = self._axes
+        if ax.tsize < 5:
+            raise ValueError("X coordinates must be larger than 4")
+        if ay.tsize < 5:
+            raise ValueError("Y  coordinates must be larger than 4")
+        if self._data.ndim != 2 or ax.tsize != self._data.shape[1]:
+            raise ValueError("X coordinates must match cols in Z matrix")
+        if ay.tsize != self._data.shape[0]:
+            raise ValueError("Y coordinates must match rows in Z matrix")
+        self._ascending(ax, "X Coordinates must be in ascending order")
+        self._ascending(ay, "Y Coordinates must be in ascending order")
+
+    def _derivs(self):
+        ax, ay = self._axes                                  # InterpTable2D.h:114-199: dz/dy, dz/dx, then d2z/dxdy as the x-stencil of dz/dy
+        zy = ay.diff(self._data, 0)
+        zx = ax.diff(self._data, 1)
+        return [self._data, zx, zy, ax.diff(zy, 1)]
+
+    def find_elem(self, vs, v) -> int:
+        """The element of the ascending `vs` that `v` falls into, not clamped (InterpTable2D.h:202-208)."""
+        return int(np.searchsorted(np.asarray(vs, dtype=float), v, side="right")) - 1
+
+
+class InterpTable3D(_InterpTableND):
+    """Tabulated data ``f(x, y, z)`` on a rectangular grid, tricubic (Hermite; nodal derivatives from five-point differences) or
+    trilinear -- the reference's ``InterpTable3D`` and ``InterpFunction3D`` (CommonFunctions/InterpTable3D.h).  ``Fs[ix, iy, iz]``
+    (numpy's ``meshgrid(..., indexing="ij")``).  ``cache`` is accepted and ignored: the reference can keep the 64 coefficients of
+    every cell; here the cell's polynomial is evaluated from its 8 x 8 corner quantities, on the host and on the device.  Host
+    calls, expression forms and the cap on embedded table data: as ``InterpTable2D``."""
+
+    _DIM, _NAME = 3, "InterpTable3D"
+
+    def __init__(self, Xs, Ys, Zs, Fs, kind="cubic", cache=False):
+        self._setup([_TableAxis(Xs, "x"), _TableAxis(Ys, "y"), _TableAxis(Zs, "z")], Fs, kind, data_axis=(0, 1, 2))
+        self.xs, self.ys, self.zs, self.fs = self._axes[0].ts, self._axes[1].ts, self._axes[2].ts, self._data
+        self.xeven, self.yeven, self.zeven = (a.teven for a in self._axes)
+        if self.kind == "cubic":
+            _, self.fs_dx, self.fs_dy, self.fs_dxdy, self.fs_dz, self.fs_dxdz, self.fs_dydz, self.fs_dxdydz = self._Q
+
+    def _check_sizes(self):
+        ax, ay, az = self._axes
+        if ax.tsize < 5:
+            raise ValueError("X coordinates must be larger than 4")
+        if ay.tsize < 5:
+            raise ValueError("Y  coordinates must be larger than 4")
+        if az.tsize < 5:
+            raise ValueError("Z  coordinates must be larger than 4")
+        if self._data.ndim != 3 or ax.tsize != self._data.shape[0]:
+            raise ValueError("X coordinates must be first dimension of value tensor")
+        if ay.tsize != self._data.shape[1]:
+            raise ValueError("Y coordinates must be second dimension of value tensor")
+        if az.tsize != self._data.shape[2]:
+            raise ValueError("Z coordinates must be third dimension of value tensor")
+        self._ascending(ax, "X coordinates must be in ascending order")
+        self._ascending(ay, "Y coordinates must be in ascending order")
+        self._ascending(az, "Z coordinates must be in ascending order")
+
+    def _derivs(self):
+        ax, ay, az = self._axes                              # InterpTable3D.h:220-228, in its order of application
+        f = self._data
+        fx, fy, fz = ax.diff(f, 0), ay.diff(f, 1), az.diff(f, 2)
+        fxy, fxz, fyz = ay.diff(fx, 1), az.diff(fx, 2), az.diff(fy, 2)
+        fxyz = az.diff(fxy, 2)
+        return [f, fx, fy, fxy, fz, fxz, fyz, fxyz]
+
+    @staticmethod
+    def find_elem(ts, teven, t) -> int:
+        """The element of `ts` that `t` falls into, clamped to [0, size - 2] (InterpTable3D.h:243-258)."""
+        ts = np.asarray(ts, dtype=float)
+        e = int((t - ts[0]) / (ts[1] - ts[0])) if teven else int(np.searchsorted(ts, t, side="right")) - 1
+        return max(min(e, ts.size - 2), 0)

@@ -36,6 +36,10 @@ COND_OPS = _COMPARE + _LOGIC
 # (functions.py: InterpTable1D), so its first and second derivatives come from the rules of this file
 TABLE_OPS = ("tabloc", "tabget")
 TABLES: Dict[str, object] = {}      # digest -> table (anything with .ts, .vs, .dvs_dts, .teven, .locate): registered by InterpTable1D
+# Tables over several axes (functions.py: InterpTable2D / InterpTable3D) register one object per AXIS (.ts, .teven, .tsize, .locate:
+# what "tabloc" and a "tabget" of the array 't' need) and one for the DATA, whose arrays are named: ``.arrays[name] = (numbers, row
+# length)``.  The argument of a "tabget" on the data is a flat index built from the axes' "tabloc" nodes -- sums and multiples of
+# piecewise-constant nodes, so piecewise constant, with no derivative, under the rules of this file.
 
 
 class Node:
@@ -261,7 +265,8 @@ class Graph:
         return self._mk("tabloc", (t,), digest)
 
     def tabget(self, digest: str, arr: str, row: int, off: int, loc: Node) -> Node:
-        """Entry ``[row, loc + off]`` of the table's array `arr` ('t': abscissae, 'v': values, 'd': nodal derivatives)."""
+        """Entry ``[row, loc + off]`` of the table's array `arr` ('t': abscissae, 'v': values, 'd': nodal derivatives; a table over
+        several axes names its own: tab_array)."""
         if loc.is_const():
             return self.const(float(_tab_entry(TABLES[digest], arr, row, int(loc.value) + off)))
         return self._mk("tabget", (loc,), (digest, arr, int(row), int(off)))
@@ -497,10 +502,19 @@ class Graph:
         return self.unary(op, args[0])
 
 
-def _tab_entry(tab, arr: str, row: int, col: int) -> float:
+def tab_array(tab, arr: str):
+    """(numbers, row length) of the array `arr` of a registered table: entry [row, col] is ``numbers[row * length + col]``."""
+    named = getattr(tab, "arrays", None)
+    if named is not None:
+        return named[arr]
     if arr == "t":
-        return tab.ts[col]
-    return (tab.vs if arr == "v" else tab.dvs_dts)[row, col]
+        return tab.ts, tab.tsize
+    return (tab.vs if arr == "v" else tab.dvs_dts).ravel(), tab.tsize
+
+
+def _tab_entry(tab, arr: str, row: int, col: int) -> float:
+    data, length = tab_array(tab, arr)
+    return data[row * length + col]
 
 
 _EVAL_COND = {"lt": lambda a, b: a < b, "le": lambda a, b: a <= b, "gt": lambda a, b: a > b, "ge": lambda a, b: a >= b}
