@@ -93,6 +93,9 @@ SYMBOLS = {
                                                C.c_int]),
     "asset_hip_propagate_events": (C.c_int, [C.c_char_p, _dp, C.c_longlong, _dp, C.POINTER(IntegOptions), C.c_int, _ip, _ip, C.c_double,
                                             C.c_int, C.c_int, _dp, _dp, _ip, _ip, _dp, _dp, _ip, _ip, _ip, C.c_int]),
+    "asset_hip_propagate_events_stm": (C.c_int, [C.c_char_p, _dp, C.c_longlong, _dp, C.POINTER(IntegOptions), C.c_int, _ip, _ip, C.c_double,
+                                                C.c_int, C.c_int, _dp, _dp, _dp, _ip, _ip, _dp, _dp, _ip, _dp, _ip, _ip, C.c_int]),
+    "asset_hip_propagate_events_stm_plan": (C.c_int, [C.c_char_p, C.c_longlong, C.POINTER(C.c_longlong)]),
     "asset_hip_rtc_module_meta": (C.c_int, [C.c_char_p, C.POINTER(C.c_longlong), C.c_int]),
     "asset_hip_event_module_sizes": (C.c_int, [C.c_char_p, _ip, _ip, _ip, _ip]),
     "asset_hip_propagate_ctrl": (C.c_int, [C.c_char_p, _dp, C.c_longlong, _dp, C.c_int, C.POINTER(IntegOptions), _dp, _dp, _ip, _ip, C.c_int]),

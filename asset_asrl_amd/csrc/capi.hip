@@ -24,6 +24,7 @@
 
 #include "registry.h"
 #include "propagate_event_kernels.h"
+#include "propagate_event_stm_kernels.h"
 #include "propagate_ctrl_kernels.h"
 #include "capi/arena.h"
 #include "capi/kkt_map.h"
@@ -364,7 +365,7 @@ int rtc_compile(const char* source, const char* functor, int kind, int mode, int
 
 int asset_hip_jit_compile(const char* source, const char* functor, int kind, int mode, int blocked, int seg_per_group,
                           const char* const* options, int noptions, const char* cache_path) {
-  if (!source || !functor || !cache_path || kind < 1 || kind > 5) return fail(ASSET_HIP_EINVAL, "bad jit arguments");
+  if (!source || !functor || !cache_path || kind < 1 || kind > 6) return fail(ASSET_HIP_EINVAL, "bad jit arguments");
   RtcBlob blob;
   const int rc = rtc_compile(source, functor, kind, mode, blocked, seg_per_group, options, noptions, blob);
   if (rc) return rc;
@@ -374,7 +375,7 @@ int asset_hip_jit_compile(const char* source, const char* functor, int kind, int
 
 int asset_hip_jit_plugin(const char* name, const char* source, const char* functor, int kind, int mode, int blocked,
                          int seg_per_group, const char* const* options, int noptions, const char* cache_path) {
-  if (!name || !functor || kind < 1 || kind > 5) return fail(ASSET_HIP_EINVAL, "bad jit arguments");
+  if (!name || !functor || kind < 1 || kind > 6) return fail(ASSET_HIP_EINVAL, "bad jit arguments");
   if (find_entry(name, kind >= 2 ? ASSET_HIP_FUNCTION : mode, kind >= 2 ? 0 : blocked)) return 0;
   RtcBlob blob;
   if (!(cache_path && rtc_read(cache_path, blob))) {
@@ -588,6 +589,8 @@ int asset_hip_defect_create(const asset_hip_defect_desc* d, asset_hip_defect_t* 
     return fail(ASSET_HIP_EINVAL, "an event module is launched through asset_hip_propagate_events, it is not a function");
   if (ke->table->meta[asset_hip::MF_KIND] == 5)
     return fail(ASSET_HIP_EINVAL, "a controller module is launched through asset_hip_propagate_ctrl*, it is not a function");
+  if (ke->table->meta[asset_hip::MF_KIND] == 6)
+    return fail(ASSET_HIP_EINVAL, "an event module is launched through asset_hip_propagate_events_stm, it is not a function");
   // (before anything is allocated: the commonest set-up error)
   if (const int rc = check_index_tables(ke, d->nseg, d->vindex, d->cindex, d->n_primal, d->n_equal)) return rc;
   if (const int rc = use_device(d->device, "no HIP device visible: the evaluator has no CPU fallback")) return rc;
@@ -673,6 +676,8 @@ int asset_hip_kkt_layout(const char* ode, int mode, int blocked, int* nkkt, int*
     return fail(ASSET_HIP_EINVAL, "an event module is launched through asset_hip_propagate_events, it is not a function");
   if (ke->table->meta[asset_hip::MF_KIND] == 5)
     return fail(ASSET_HIP_EINVAL, "a controller module is launched through asset_hip_propagate_ctrl*, it is not a function");
+  if (ke->table->meta[asset_hip::MF_KIND] == 6)
+    return fail(ASSET_HIP_EINVAL, "an event module is launched through asset_hip_propagate_events_stm, it is not a function");
   if (nkkt) *nkkt = ke->nkkt;
   return entry_kkt_layout(ke, stride, rows, cols);
 }
@@ -716,6 +721,8 @@ int asset_hip_launch_plan_query(const char* ode, int mode, int blocked, int what
     return fail(ASSET_HIP_EINVAL, "an event module is launched through asset_hip_propagate_events, it is not a function");
   if (ke->table->meta[asset_hip::MF_KIND] == 5)
     return fail(ASSET_HIP_EINVAL, "a controller module is launched through asset_hip_propagate_ctrl*, it is not a function");
+  if (ke->table->meta[asset_hip::MF_KIND] == 6)
+    return fail(ASSET_HIP_EINVAL, "an event module is launched through asset_hip_propagate_events_stm, it is not a function");
   return entry_launch_plan(ke, what, assembled, nseg, cus, asset_hip::entry_lane_bytes(ke, 0) > 0, out);
 }
 int asset_hip_defect_launch_plan(asset_hip_defect_t h, int what, int assembled, asset_hip_launch_plan* out) {
@@ -725,7 +732,7 @@ int asset_hip_defect_launch_plan(asset_hip_defect_t h, int what, int assembled, 
 const char* asset_hip_kernel_slot_name(int slot) { return asset_hip::kslot_name(slot); }
 int asset_hip_kernel_slot_kinds(int slot) {
   int kinds = 0;
-  for (int kind = 1; kind <= 5; kind++)
+  for (int kind = 1; kind <= 6; kind++)
     if (!asset_hip::rtc_kernel_expr(slot, kind, "F", ASSET_HIP_LGL3, false, 1).empty()) kinds |= 1 << (kind - 1);
   return kinds;
 }
@@ -1049,6 +1056,14 @@ const asset_hip::KernelEntry* event_entry(const char* module) {
   return (ke && ke->table->meta[asset_hip::MF_KIND] == 4 && ke->table->k[asset_hip::K_PROP_EVENT]) ? ke : nullptr;
 }
 
+// ... propagated with its state-transition matrix: a run-time module of kind 6
+const asset_hip::KernelEntry* event_stm_entry(const char* module) {
+  const asset_hip::KernelEntry* ke = find_entry(module, ASSET_HIP_FUNCTION, 0);
+  const bool ok = ke && ke->table->meta[asset_hip::MF_KIND] == 6 && ke->table->k[asset_hip::K_PROP_EVENT_STM] &&
+                  ke->table->k[asset_hip::K_PROP_EVENT_JAC];
+  return ok ? ke : nullptr;
+}
+
 // an ODE with its control law: a run-time module of kind 5 (asset_hip_jit_plugin), registered under its own name
 const asset_hip::KernelEntry* ctrl_entry(const char* module) {
   const asset_hip::KernelEntry* ke = find_entry(module, ASSET_HIP_FUNCTION, 0);
@@ -1074,7 +1089,8 @@ int prop_checked(long long m, int ns, const asset_hip_integ_options* opt, const 
   return use_device(device, "no HIP device visible: the propagation has no CPU fallback");
 }
 
-// y0 | tf | abs | rel at the head of the doubles and steps | status at the head of the ints (Args: PropArgs, PropCtrlArgs, PropEventArgs)
+// y0 | tf | abs | rel at the head of the doubles and steps | status at the head of the ints (Args: PropArgs, PropCtrlArgs, PropEventArgs,
+// PropEventStmArgs)
 template <class Args>
 void problems_take(IntegCall& c, Args& a, size_t m, int N, int n) {
   c.d.take(&a.y0, m * N), c.d.take(&a.tf, m), c.d.take(&a.abs_tols, n), c.d.take(&a.rel_tols, n);
@@ -1127,6 +1143,82 @@ int propagate_impl(const char* name, const double* y0, long long m, const double
   HIP_TRY_AS(hipDeviceSynchronize(), ctrl ? "controller propagation kernels" : "propagation kernels");
   return c.download({{xs, a.xs, sz_x, "states"}, {us, d_us, sz_u, "controls"}, {jac, a.jac, sz_l * (N + 1), "jac"},
                      {xf_last, a.xlast, sz_l, "xf_last"}, {steps, a.steps, um * 2, "steps"}, {status, a.status, um, "status"}});
+}
+// the launch plan of a propagation with events: a lane per problem, or with the STM the plan of prop_stm_kernel unchanged
+asset_hip::PropPlan event_plan(const asset_hip::KernelEntry* ke, long long m, bool stm) {
+  return asset_hip::propagate_plan(ke->xv, ke->uv, ke->pv, m, stm ? 1 : 0);
+}
+
+// asset_hip_propagate_events (Args = PropEventArgs: a module of kind 4, no `jac` / `ev_jac`) and asset_hip_propagate_events_stm
+// (PropEventStmArgs: a module of kind 6; `ev_jac` may be null, then ev_S is neither allocated nor written)
+template <class Args>
+int propagate_events_impl(const char* module, const double* y0, long long m, const double* tf, const asset_hip_integ_options* opt, int ne,
+                          const int* direction, const int* stop, double event_tol, int max_event_iters, int max_locs, double* xf, double* jac,
+                          double* t_end, int* stopped, int* ev_count, double* ev_rows, double* ev_resid, int* ev_conv, double* ev_jac,
+                          int* steps, int* status, int device) {
+  constexpr bool stm = std::is_same<Args, asset_hip::PropEventStmArgs>::value;
+  if (!module || !y0 || !tf || !direction || !stop || !xf || (stm && !jac) || !t_end || !stopped || !ev_count || !ev_rows || !ev_resid ||
+      !ev_conv)
+    return fail(ASSET_HIP_EINVAL, "null argument");
+  const asset_hip::KernelEntry* ke = nullptr;
+  Args a{};
+  asset_hip::PropPlan plan;
+  const int bad = prop_checked(m, 1, opt, tf, device, a.opt, plan, [&](asset_hip::PropPlan& p) {
+    ke = stm ? event_stm_entry(module) : event_entry(module);
+    if (!ke && (stm ? event_entry(module) : event_stm_entry(module)))
+      return fail(ASSET_HIP_ENOODE, std::string("'") + module + "' is an event module of kind " + (stm ? "4" : "6") + ": this call takes one of kind " +
+                                        (stm ? "6 (asset_hip_propagate_events takes it)" : "4 (asset_hip_propagate_events_stm takes it)"));
+    if (!ke)
+      return fail(ASSET_HIP_ENOODE, std::string("no event module registered as '") + module + "' (asset_hip_jit_plugin, kind " + (stm ? "6)" : "4)"));
+    if (ne != ke->orr) return fail(ASSET_HIP_EINVAL, "ne is " + std::to_string(ne) + " but the module has " + std::to_string(ke->orr) + " events");
+    if (!(event_tol > 0.0)) return fail(ASSET_HIP_EINVAL, "event_tol must be positive");
+    if (max_event_iters < 1) return fail(ASSET_HIP_EINVAL, "max_event_iters must be at least 1");
+    if (max_locs < 1) return fail(ASSET_HIP_EINVAL, "max_locs must be at least 1");
+    for (int j = 0; j < ne; j++) {
+      if (direction[j] < -1 || direction[j] > 1) return fail(ASSET_HIP_EINVAL, "direction must be -1, 0 or 1 (event " + std::to_string(j) + ")");
+      if (stop[j] < 0) return fail(ASSET_HIP_EINVAL, "stop must not be negative (event " + std::to_string(j) + ")");
+      if (stop[j] > max_locs)
+        return fail(ASSET_HIP_EINVAL, "stop exceeds max_locs: the stopping occurrence would not be located (event " + std::to_string(j) + ")");
+    }
+    p = event_plan(ke, m, stm);
+    return 0;
+  });
+  if (bad) return bad;
+  const int n = ke->xv, N = ke->xv + 1 + ke->uv + ke->pv, C = N - 1;
+  // one allocation of doubles: y0 | tf | abs | rel | xf | t_end | ev_rows | ev_resid | (stm: S | jac | (ev_jac wanted: ev_S | ev_jac));
+  // one of ints: steps | status | stopped | ev_count | ev_conv
+  const size_t um = size_t(m), sz_x = um * n, sz_e = um * ne * size_t(max_locs), sz_r = sz_e * (n + 1), sz_c = um * ne;
+  const size_t sz_j = stm ? sz_x * (N + 1) : 0, sz_ej = stm && ev_jac ? sz_e * n * (N + 1) : 0;
+  a.m = m, a.lanes = plan.lanes, a.max_iters = max_event_iters, a.max_locs = max_locs, a.event_tol = event_tol;
+  for (int j = 0; j < asset_hip::PROP_EVENT_MAX; j++) a.direction[j] = j < ne ? direction[j] : 0, a.stop[j] = j < ne ? stop[j] : 0;
+  double* d_jac = nullptr;
+  double* d_ev_jac = nullptr;
+  IntegCall c;
+  problems_take(c, a, um, N, n);
+  c.d.take(&a.xf, sz_x), c.d.take(&a.t_end, um), c.d.take(&a.ev_rows, sz_r), c.d.take(&a.ev_resid, sz_e);
+  if constexpr (stm) {
+    a.group = plan.group, a.passes = plan.passes;
+    c.d.take(&a.S, sz_x * C), c.d.take(&a.jac, sz_j);
+    c.d.take(ev_jac ? &a.ev_S : nullptr, ev_jac ? sz_e * n * C : 0), c.d.take(ev_jac ? &a.ev_jac : nullptr, sz_ej);
+  }
+  c.i.take(&a.stopped, um), c.i.take(&a.ev_count, sz_c), c.i.take(&a.ev_conv, sz_e);
+  if (const int rc = c.allocate()) return rc;
+  if (const int rc = c.upload(a.y0, y0, um * N, "y0", a.abs_tols, opt, n, a.tf, tf, um)) return rc;
+  if constexpr (stm) d_jac = a.jac, d_ev_jac = a.ev_jac;
+  void* kargs[] = {&a};
+  HIP_TRY_AS(asset_hip::klaunch(ke->table->k[stm ? asset_hip::K_PROP_EVENT_STM : asset_hip::K_PROP_EVENT], dim3(unsigned(plan.grid)), dim3(64),
+                                size_t(plan.lds_bytes), nullptr, kargs), "event propagation kernel");
+  if (stm) {
+    const size_t items = um * (ev_jac ? 1 + size_t(ne) * size_t(max_locs) : 1);
+    if ((items + 63) / 64 > 0x7fffffffULL) return fail(ASSET_HIP_EINVAL, "the batch does not fit one launch (workgroups or LDS)");
+    HIP_TRY_AS(asset_hip::klaunch(ke->table->k[asset_hip::K_PROP_EVENT_JAC], dim3(unsigned((items + 63) / 64)), dim3(64), 0, nullptr, kargs),
+               "event STM assembly kernel");
+  }
+  HIP_TRY_AS(hipDeviceSynchronize(), "event propagation kernel");
+  return c.download({{xf, a.xf, sz_x, "states"}, {jac, d_jac, sz_j, "jac"}, {t_end, a.t_end, um, "t_end"}, {ev_rows, a.ev_rows, sz_r, "ev_rows"},
+                     {ev_resid, a.ev_resid, sz_e, "ev_resid"}, {ev_jac, d_ev_jac, sz_ej, "ev_jac"}, {stopped, a.stopped, um, "stopped"},
+                     {ev_count, a.ev_count, sz_c, "ev_count"}, {ev_conv, a.ev_conv, sz_e, "ev_conv"}, {steps, a.steps, um * 2, "steps"},
+                     {status, a.status, um, "status"}});
 }
 }  // namespace
 
@@ -1212,6 +1304,7 @@ int asset_hip_propagate_stm_lanes(const char* ode, const double* y0, long long m
 int asset_hip_event_module_sizes(const char* module, int* xv, int* uv, int* pv, int* ne) {
   if (!module) return fail(ASSET_HIP_EINVAL, "null argument");
   const asset_hip::KernelEntry* ke = event_entry(module);
+  if (!ke) ke = event_stm_entry(module);             // (a module of kind 4 or of kind 6: the same fields)
   if (!ke) return fail(ASSET_HIP_ENOODE, std::string("no event module registered as '") + module + "'");
   if (xv) *xv = ke->xv;
   if (uv) *uv = ke->uv;
@@ -1224,46 +1317,27 @@ int asset_hip_propagate_events(const char* module, const double* y0, long long m
                                int ne, const int* direction, const int* stop, double event_tol, int max_event_iters, int max_locs,
                                double* xf, double* t_end, int* stopped, int* ev_count, double* ev_rows, double* ev_resid, int* ev_conv,
                                int* steps, int* status, int device) {
-  if (!module || !y0 || !tf || !direction || !stop || !xf || !t_end || !stopped || !ev_count || !ev_rows || !ev_resid || !ev_conv)
-    return fail(ASSET_HIP_EINVAL, "null argument");
-  const asset_hip::KernelEntry* ke = nullptr;
-  asset_hip::PropEventArgs a{};
-  asset_hip::PropPlan plan;
-  const int bad = prop_checked(m, 1, opt, tf, device, a.opt, plan, [&](asset_hip::PropPlan& p) {
-    ke = event_entry(module);
-    if (!ke) return fail(ASSET_HIP_ENOODE, std::string("no event module registered as '") + module + "' (asset_hip_jit_plugin, kind 4)");
-    if (ne != ke->orr) return fail(ASSET_HIP_EINVAL, "ne is " + std::to_string(ne) + " but the module has " + std::to_string(ke->orr) + " events");
-    if (!(event_tol > 0.0)) return fail(ASSET_HIP_EINVAL, "event_tol must be positive");
-    if (max_event_iters < 1) return fail(ASSET_HIP_EINVAL, "max_event_iters must be at least 1");
-    if (max_locs < 1) return fail(ASSET_HIP_EINVAL, "max_locs must be at least 1");
-    for (int j = 0; j < ne; j++) {
-      if (direction[j] < -1 || direction[j] > 1) return fail(ASSET_HIP_EINVAL, "direction must be -1, 0 or 1 (event " + std::to_string(j) + ")");
-      if (stop[j] < 0) return fail(ASSET_HIP_EINVAL, "stop must not be negative (event " + std::to_string(j) + ")");
-      if (stop[j] > max_locs)
-        return fail(ASSET_HIP_EINVAL, "stop exceeds max_locs: the stopping occurrence would not be located (event " + std::to_string(j) + ")");
-    }
-    p = asset_hip::propagate_plan(ke->xv, ke->uv, ke->pv, m, 0);
-    return 0;
-  });
-  if (bad) return bad;
-  const int n = ke->xv, N = ke->xv + 1 + ke->uv + ke->pv;
-  // one allocation of doubles: y0 | tf | abs | rel | xf | t_end | ev_rows | ev_resid; one of ints: steps | status | stopped | ev_count | ev_conv
-  const size_t um = size_t(m), sz_x = um * n, sz_e = um * ne * size_t(max_locs), sz_r = sz_e * (n + 1), sz_c = um * ne;
-  a.m = m, a.lanes = plan.lanes, a.max_iters = max_event_iters, a.max_locs = max_locs, a.event_tol = event_tol;
-  for (int j = 0; j < asset_hip::PROP_EVENT_MAX; j++) a.direction[j] = j < ne ? direction[j] : 0, a.stop[j] = j < ne ? stop[j] : 0;
-  IntegCall c;
-  problems_take(c, a, um, N, n);
-  c.d.take(&a.xf, sz_x), c.d.take(&a.t_end, um), c.d.take(&a.ev_rows, sz_r), c.d.take(&a.ev_resid, sz_e);
-  c.i.take(&a.stopped, um), c.i.take(&a.ev_count, sz_c), c.i.take(&a.ev_conv, sz_e);
-  if (const int rc = c.allocate()) return rc;
-  if (const int rc = c.upload(a.y0, y0, um * N, "y0", a.abs_tols, opt, n, a.tf, tf, um)) return rc;
-  void* kargs[] = {&a};
-  HIP_TRY_AS(asset_hip::klaunch(ke->table->k[asset_hip::K_PROP_EVENT], dim3(unsigned(plan.grid)), dim3(64), size_t(plan.lds_bytes), nullptr,
-                                kargs), "event propagation kernel");
-  HIP_TRY_AS(hipDeviceSynchronize(), "event propagation kernel");
-  return c.download({{xf, a.xf, sz_x, "states"}, {t_end, a.t_end, um, "t_end"}, {ev_rows, a.ev_rows, sz_r, "ev_rows"},
-                     {ev_resid, a.ev_resid, sz_e, "ev_resid"}, {stopped, a.stopped, um, "stopped"}, {ev_count, a.ev_count, sz_c, "ev_count"},
-                     {ev_conv, a.ev_conv, sz_e, "ev_conv"}, {steps, a.steps, um * 2, "steps"}, {status, a.status, um, "status"}});
+  return propagate_events_impl<asset_hip::PropEventArgs>(module, y0, m, tf, opt, ne, direction, stop, event_tol, max_event_iters, max_locs, xf,
+                                                         nullptr, t_end, stopped, ev_count, ev_rows, ev_resid, ev_conv, nullptr, steps, status,
+                                                         device);
+}
+int asset_hip_propagate_events_stm_plan(const char* module, long long m, long long* out) {
+  if (!module || !out) return fail(ASSET_HIP_EINVAL, "null argument");
+  const asset_hip::KernelEntry* ke = event_stm_entry(module);
+  if (!ke) return fail(ASSET_HIP_ENOODE, std::string("no event module of kind 6 registered as '") + module + "'");
+  const asset_hip::PropPlan p = event_plan(ke, m, true);
+  if (p.grid < 1) return fail(ASSET_HIP_EINVAL, "m must be at least 1");
+  const long long v[7] = {p.group, p.lanes, p.passes, p.problems_per_wg, p.lds_bytes, p.grid, p.columns};
+  for (int k = 0; k < 7; k++) out[k] = v[k];
+  return 0;
+}
+int asset_hip_propagate_events_stm(const char* module, const double* y0, long long m, const double* tf, const asset_hip_integ_options* opt,
+                                   int ne, const int* direction, const int* stop, double event_tol, int max_event_iters, int max_locs,
+                                   double* xf, double* jac, double* t_end, int* stopped, int* ev_count, double* ev_rows, double* ev_resid,
+                                   int* ev_conv, double* ev_jac, int* steps, int* status, int device) {
+  return propagate_events_impl<asset_hip::PropEventStmArgs>(module, y0, m, tf, opt, ne, direction, stop, event_tol, max_event_iters, max_locs,
+                                                            xf, jac, t_end, stopped, ev_count, ev_rows, ev_resid, ev_conv, ev_jac, steps,
+                                                            status, device);
 }
 
 // ---- propagation with a controller (propagate_ctrl_kernels.h): propagate_impl against a module of kind 5

@@ -15,7 +15,8 @@
 namespace asset_hip {
 
 enum MetaField {
-  MF_KIND = 0,       // 1: transcription of an ODE, 2: plain function, 3: bundle of plain functions, 4: an ODE with event functions, 5: an ODE with a control law
+  MF_KIND = 0,       // 1: transcription of an ODE, 2: plain function, 3: bundle of plain functions, 4: an ODE with event functions, 5: an ODE with a control law,
+                     // 6: an ODE with event functions, propagated with its state-transition matrix
   MF_XV, MF_UV, MF_PV,
   MF_MODE,           // ASSET_HIP_* transcription id (0 for plain functions)
   MF_BLOCKED,
@@ -97,6 +98,13 @@ struct BundleMeta {
 template <class Ode, class Ev>
 struct EventMeta {
   static constexpr long long v[MF_COUNT] = {4, Ode::XV, Ode::UV, Ode::PV, 0, 0, Ode::NIN, Ev::XV};
+};
+
+// An ODE with its event functions, propagated with the state-transition matrix (propagate_event_stm_kernels.h: prop_event_stm_kernel,
+// prop_event_jac_kernel <Ode, Ev>): MF_KIND 6, the fields of EventMeta.  Read from the code object on the host, like that table.
+template <class Ode, class Ev>
+struct EventStmMeta {
+  static constexpr long long v[MF_COUNT] = {6, Ode::XV, Ode::UV, Ode::PV, 0, 0, Ode::NIN, Ev::XV};
 };
 
 // An ODE with its control law (propagate_ctrl_kernels.h: prop_ctrl_*_kernel<Ode, Ctl>): MF_KIND 5, the ODE's sizes, MF_IR = its input

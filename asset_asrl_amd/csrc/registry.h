@@ -118,7 +118,8 @@ inline hipError_t klaunch(const KRef& k, dim3 grid, dim3 block, size_t shmem, hi
 // ODE: <Ode, ...> (kernels of the ODE alone, whatever the transcription: they live in ONE entry per ODE, prop_home below),
 // FUNC: <F, ...> (plain functions), BUNDLE: <..., Fs...> (bundles, run-time modules only), ODEEV: <Ode, Ev, ...> (an ODE with an event
 // functor, run-time modules only: rtc_device.h, ASSET_RTC_PROP_EVENTS), ODECTL: <Ode, Ctl, ...> (an ODE with its control law, run-time
-// modules only: ASSET_RTC_PROP_CTRL) -- and the condition is the compile-time
+// modules only: ASSET_RTC_PROP_CTRL), ODEEVS: <Ode, Ev, ...> (an ODE with an event functor, propagated with its STM, run-time modules
+// only: ASSET_RTC_PROP_EVENTS_STM) -- and the condition is the compile-time
 // one (D = Dims<Ode, SCH, BLOCKED>) under which a shape linked into the library has the kernel.  The slot enum, the static tables
 // (lgl_static_table, func_static_table) and the name expressions of a run-time module (rtc_kernel_expr, which names every slot of
 // its kind: rtc_device.h compiles the variants a shape lacks to empty kernels) are all generated from this list.
@@ -203,7 +204,10 @@ constexpr bool prop_home(int sch, bool blocked) { return sch == PROP_HOME_MODE &
   /* propagation with a controller (propagate_ctrl_kernels.h): the ODE's functor and the law's in one run-time module */         \
   X(K_PROP_CTRL_BATCH, ODECTL, true, prop_ctrl_batch_kernel)                                                                     \
   X(K_PROP_CTRL_STM, ODECTL, true, prop_ctrl_stm_kernel)                                                                         \
-  X(K_PROP_CTRL_JAC, ODECTL, true, prop_ctrl_jac_kernel)
+  X(K_PROP_CTRL_JAC, ODECTL, true, prop_ctrl_jac_kernel)                                                                         \
+  /* propagation with events and the STM (propagate_event_stm_kernels.h): a run-time module of its own kind */                  \
+  X(K_PROP_EVENT_STM, ODEEVS, true, prop_event_stm_kernel)                                                                       \
+  X(K_PROP_EVENT_JAC, ODEEVS, true, prop_event_jac_kernel)
 
 #define ASSET_X_ENUM(NAME, ...) NAME,
 enum KSlot : int { ASSET_KERNELS(ASSET_X_ENUM) K_COUNT };
@@ -615,6 +619,7 @@ inline hipError_t entry_lane_setup(const KernelEntry* ke, int level, void* out, 
 #define ASSET_FILL_BUNDLE(NAME, COND, T, ...)
 #define ASSET_FILL_ODEEV(NAME, COND, T, ...)
 #define ASSET_FILL_ODECTL(NAME, COND, T, ...)
+#define ASSET_FILL_ODEEVS(NAME, COND, T, ...)
 #define ASSET_X_FILL(NAME, FAMILY, COND, T, ...) ASSET_FILL_##FAMILY(NAME, COND, T, ##__VA_ARGS__)
 template <class Ode, int SCH, bool BLOCKED, int G>
 const KernelTable* lgl_static_table() {
@@ -655,6 +660,7 @@ const KernelTable* func_static_table() {
 #undef ASSET_FILL_BUNDLE
 #undef ASSET_FILL_ODEEV
 #undef ASSET_FILL_ODECTL
+#undef ASSET_FILL_ODEEVS
 #undef ASSET_X_FILL
 #undef ASSET_KPTR
 
@@ -678,7 +684,8 @@ struct StaticEntry {   // (static initialisation: the table is filled and the en
 
 // ---- name expressions of the kernels of a run-time module (capi.hip: asset_hip_jit_plugin) -----------------------------
 // kind 1: `type` is the ODE functor, kind 2: the function functor, kind 3: the comma-separated functor list of a bundle, kind 4: "Ode, Ev",
-// the ODE functor and the event functor of a propagation with events, kind 5: "Ode, Ctl", the ODE functor and its control law.  Slots
+// the ODE functor and the event functor of a propagation with events, kind 5: "Ode, Ctl", the ODE functor and its control law, kind 6: "Ode, Ev"
+// again, for the propagation with events and the STM.  Slots
 // without a kernel for that kind: empty string.
 inline std::string rtc_kernel_expr(int slot, int kind, const std::string& type, int csv, bool blocked, int g) {
   const std::string none, lgl = type + ", " + std::to_string(csv) + ", " + (blocked ? "true" : "false"), lglg = lgl + ", " + std::to_string(g);
@@ -696,6 +703,7 @@ inline std::string rtc_kernel_expr(int slot, int kind, const std::string& type, 
 #define ASSET_RTC_BUNDLE 3, type, true
 #define ASSET_RTC_ODEEV 4, type
 #define ASSET_RTC_ODECTL 5, type
+#define ASSET_RTC_ODEEVS 6, type
 #define ASSET_X_EXPR(NAME, FAMILY, COND, T, ...) case NAME: return expr(#T, #__VA_ARGS__, ASSET_RTC_##FAMILY);
   switch (slot) { ASSET_KERNELS(ASSET_X_EXPR) }
 #undef ASSET_X_EXPR
@@ -707,6 +715,7 @@ inline std::string rtc_kernel_expr(int slot, int kind, const std::string& type, 
 #undef ASSET_RTC_BUNDLE
 #undef ASSET_RTC_ODEEV
 #undef ASSET_RTC_ODECTL
+#undef ASSET_RTC_ODEEVS
   return "";
 }
 

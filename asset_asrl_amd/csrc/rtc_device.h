@@ -5,6 +5,7 @@
 //     ASSET_RTC_LGL(OdeName, CSV, BLK, G)   or   ASSET_RTC_FUNC(FnName)   or   ASSET_RTC_BUNDLE(Fn0, Fn1, ...)
 //     or   ASSET_RTC_PROP_EVENTS(OdeName, EvName)   (both functors in the one source: propagate_event_kernels.h)
 //     or   ASSET_RTC_PROP_CTRL(OdeName, CtlName)    (an ODE and its control law in the one source: propagate_ctrl_kernels.h)
+//     or   ASSET_RTC_PROP_EVENTS_STM(OdeName, EvName)   (as ASSET_RTC_PROP_EVENTS, with the STM: propagate_event_stm_kernels.h)
 // and the loader names the kernels it wants (hiprtcAddNameExpression): every variant the launcher of registry.h may use.
 // Variants a shape does not have compile to empty kernels (lgl_variant_valid, the guards of the wide / units / setup
 // kernels), so the list does not depend on the shape.
@@ -15,6 +16,7 @@
 #include "mesh_kernels.h"
 #include "propagate_kernels.h"
 #include "propagate_event_kernels.h"
+#include "propagate_event_stm_kernels.h"
 #include "propagate_ctrl_kernels.h"
 
 #define ASSET_RTC_LGL(ODE, CSV, BLK, G)                                                                            \
@@ -32,6 +34,9 @@
 #define ASSET_RTC_PROP_CTRL(ODE, CTL)                                                                              \
   extern "C" __device__ const long long asset_rtc_meta[::asset_hip::MF_COUNT] = {                                  \
       ASSET_RTC_META_LIST((::asset_hip::CtrlMeta<ODE, CTL>::v))};
+#define ASSET_RTC_PROP_EVENTS_STM(ODE, EV)                                                                         \
+  extern "C" __device__ const long long asset_rtc_meta[::asset_hip::MF_COUNT] = {                                  \
+      ASSET_RTC_META_LIST((::asset_hip::EventStmMeta<ODE, EV>::v))};
 // (an array cannot be initialised from another array: spell the elements out)
 #define ASSET_RTC_META_LIST(V)                                                                                     \
   V[0], V[1], V[2], V[3], V[4], V[5], V[6], V[7], V[8], V[9], V[10], V[11], V[12], V[13], V[14], V[15], V[16], V[17],  \

@@ -1,6 +1,6 @@
 """``ode.integrator(...)``: batched propagation of an ODE on the device (csrc/propagate_kernels.h, csrc/propagate_event_kernels.h,
-csrc/propagate_ctrl_kernels.h; include/asset_hip.h: asset_hip_propagate, asset_hip_propagate_stm, asset_hip_propagate_events,
-asset_hip_propagate_ctrl, asset_hip_propagate_ctrl_stm).
+csrc/propagate_event_stm_kernels.h, csrc/propagate_ctrl_kernels.h; include/asset_hip.h: asset_hip_propagate, asset_hip_propagate_stm,
+asset_hip_propagate_events, asset_hip_propagate_events_stm, asset_hip_propagate_ctrl, asset_hip_propagate_ctrl_stm).
 
 The reference's ``Integrator`` (Integrators/Integrator.h) in its own method names and return shapes: rows go in and come out as full
 ``[x, t, u, p]`` rows.  WITHOUT a controller the controls and parameters of a row are held for the whole propagation
@@ -36,6 +36,19 @@ count towards ``stop``.  The event functions are compiled with the ODE into one 
 Locating does not disturb the propagation: the end state and step counts of a problem whose events never stop it are those of the
 call without events, bit for bit.
 
+Events with the state-transition matrix (Integrator.h:2076-2082, :2125): ``integrate_events_stm(x0, tf, events)`` and
+``integrate_events_stm_parallel(x0s, tfs, events)`` return ``(row, J, eventlocs)`` per problem, the reference's ``STMEventRet``, from
+ONE propagation: the row and ``eventlocs`` are those of ``integrate_parallel(x0s, tfs, events)`` bit for bit, and ``J`` is the Jacobian
+of the row's state -- the state at which the propagation STOPPED when an event stopped it -- in the layout above, its last column
+``f`` at the end state and at the END TIME (not ``tf`` when the problem stopped).  What differential correction onto a surface of section
+needs is one call.  With ``event_jacs=True`` every entry of ``eventlocs[j]`` is ``(row, J_loc)``, ``J_loc`` the same Jacobian of the located
+state: the discrete derivative through the accepted steps up to the start of the bracketing step, then the one step of size
+``theta h`` with ``theta`` HELD -- the derivative of the crossing with the event condition eliminated, ``J - f (grad g J) / (grad g f)``,
+is left to the caller, who has ``J_loc`` and its last column ``f``.  A lane group of the STM kernel runs the event state machine in
+lockstep and carries its column through every trip, a location's ``theta h`` step included.  These are NEW METHOD NAMES because the
+``events=`` keyword of ``integrate_stm`` / ``integrate_stm_parallel`` is pinned to ``NotImplementedError`` by the tests of the events
+work; routing that keyword here is a one-line follow-up for a change that may edit those tests.
+
 Controllers (Integrator.h:96-118, 190-249, 373-381, 398-463): ``ode.integrator(def_step, ucon, varlocs)`` -- ``ucon`` a ``vf`` function
 with ``IRows() == len(varlocs)`` and ``ORows() == UV``, ``varlocs`` an int or a sequence of ints indexing the ODE's input row -- evaluates
 ``u = ucon(row[varlocs])`` at every Runge-Kutta stage, the row that stage's ``[x_s, t_s, ., p]``; the textbook call is tangential thrust,
@@ -49,7 +62,9 @@ The law is compiled with the ODE into one module per (ODE, law, varlocs) at firs
 ``ode.integrator(def_step, v)``, ``v`` a number or ``UV`` numbers, is the constant controller (Integrator.h:111-118): ``v`` is written
 into the rows' control columns and the held-control kernels run.
 
-Out of scope: dense output with events and the STM with events (``NotImplementedError``); events with a controller; ``integrate_stm2``
+Out of scope: dense output with events (its sample times depend on an end time that is not known until the propagation stops), and
+the ``events=`` keyword of ``integrate_stm*`` (``NotImplementedError``: use ``integrate_events_stm*``); events, with or without the STM,
+under a control law; ``integrate_stm2``
 (second derivatives); the trajectory-table controller ``integrator(def_step, table[, ulocs])`` (a ``u(t)`` law can be written with
 ``vf.InterpTable1D``); DOPRI54; ``calc_global_error`` (one serial propagation, not a batch).  ``Phase.AutoScaling`` does not enter: this is an ODE-level
 feature and works in the ODE's own units.
@@ -130,7 +145,7 @@ class Integrator(IntegratorOptions):
         self._name = None
         self._ctrl_module = None
         self.EventTol, self.MaxEventIters, self.MaxEventLocs = 1.0e-6, 10, 8      # Integrator.h:304-305; stored occurrences per event
-        self._event_modules = {}
+        self._event_modules, self._event_stm_modules = {}, {}
 
     # ---- plumbing
     def _width(self):
@@ -247,31 +262,42 @@ class Integrator(IntegratorOptions):
             raise ValueError(f"a stop count exceeds MaxEventLocs = {int(self.MaxEventLocs)}: the stopping occurrence would not be located")
         return funcs, direction, stop
 
-    def _event_module(self, funcs):
+    def _event_module(self, funcs, stm=False):
         key = tuple(id(g) for g in funcs)
-        hit = self._event_modules.get(key)
+        cache = self._event_stm_modules if stm else self._event_modules
+        hit = cache.get(key)
         if hit is None or any(a is not b for a, b in zip(hit[1], funcs)):
             from . import jit
-            hit = (jit.ensure_event_module(self.ode, funcs, compile_only=False), list(funcs))
-            self._event_modules[key] = hit
+            ensure = jit.ensure_event_stm_module if stm else jit.ensure_event_module
+            hit = (ensure(self.ode, funcs, compile_only=False), list(funcs))
+            cache[key] = hit
         return hit[0]
 
-    def _call_events(self, Y, T, funcs, direction, stop):
+    def _call_events(self, Y, T, funcs, direction, stop, stm=False, event_jacs=False):
         """asset_hip_propagate_events as it is: dict of xf[m, n], t_end[m], stopped[m], ev_count[m, ne], ev_rows[m, ne, K, n + 1],
-        ev_resid[m, ne, K], ev_conv[m, ne, K], steps[m, 2], status[m]."""
+        ev_resid[m, ne, K], ev_conv[m, ne, K], steps[m, 2], status[m].  ``stm``: asset_hip_propagate_events_stm, also jac[m, n, N + 1]
+        and, with ``event_jacs``, ev_jac[m, ne, K, n, N + 1]."""
         m, n, ne, K = Y.shape[0], self.xv, len(funcs), int(self.MaxEventLocs)
-        module = self._event_module(funcs)
+        module = self._event_module(funcs, stm)
         r = dict(xf=np.empty((m, n)), t_end=np.empty(m), stopped=np.empty(m, dtype=np.int32), ev_count=np.empty((m, ne), dtype=np.int32),
                  ev_rows=np.empty((m, ne, K, n + 1)), ev_resid=np.empty((m, ne, K)), ev_conv=np.empty((m, ne, K), dtype=np.int32),
                  steps=np.empty((m, 2), dtype=np.int32), status=np.empty(m, dtype=np.int32))
-        self._call("asset_hip_propagate_events", module, Y, T, None, ne, direction, stop, float(self.EventTol), int(self.MaxEventIters), K,
-                   r["xf"], r["t_end"], r["stopped"], r["ev_count"], r["ev_rows"], r["ev_resid"], r["ev_conv"], r["steps"], r["status"])
+        head = (ne, direction, stop, float(self.EventTol), int(self.MaxEventIters), K)
+        if stm:
+            r["jac"] = np.empty((m, n, self._width() + 1))
+            if event_jacs:
+                r["ev_jac"] = np.empty((m, ne, K, n, self._width() + 1))
+            self._call("asset_hip_propagate_events_stm", module, Y, T, None, *head, r["xf"], r["jac"], r["t_end"], r["stopped"], r["ev_count"],
+                       r["ev_rows"], r["ev_resid"], r["ev_conv"], r.get("ev_jac"), r["steps"], r["status"])
+        else:
+            self._call("asset_hip_propagate_events", module, Y, T, None, *head, r["xf"], r["t_end"], r["stopped"], r["ev_count"], r["ev_rows"],
+                       r["ev_resid"], r["ev_conv"], r["steps"], r["status"])
         return r
 
-    def _propagate_events(self, Y, T, events, details):
+    def _propagate_events(self, Y, T, events, details, stm=False, event_jacs=False):
         funcs, direction, stop = self._events(events)
         m, n, ne, K = Y.shape[0], self.xv, len(funcs), int(self.MaxEventLocs)
-        r = self._call_events(Y, T, funcs, direction, stop)
+        r = self._call_events(Y, T, funcs, direction, stop, stm, event_jacs)
         if not details:
             self._raise_unless_ok(r["status"])
         rows = Y.copy()
@@ -286,13 +312,16 @@ class Integrator(IntegratorOptions):
         gc.disable()                    # (m (ne + 2) containers, none of them garbage: the collector's passes over them triple the time)
         try:
             locs = [[[] for _ in range(ne)] for _ in range(m)]
-            for (i, j), row in zip(idx[:, :2].tolist(), list(located)):
+            entries = list(located)
+            if stm and event_jacs:                  # (row, J_loc)
+                entries = list(zip(entries, list(r["ev_jac"][idx[:, 0], idx[:, 1], idx[:, 2]])))
+            for (i, j), row in zip(idx[:, :2].tolist(), entries):
                 locs[i][j].append(row)
-            res = list(zip(list(rows), locs))
+            res = list(zip(list(rows), list(r["jac"]), locs)) if stm else list(zip(list(rows), locs))
         finally:
             if collecting:
                 gc.enable()
-        info = {k: r[k] for k in ("steps", "status", "stopped", "t_end", "ev_count", "ev_rows", "ev_resid", "ev_conv")}
+        info = {k: r[k] for k in ("steps", "status", "stopped", "t_end", "ev_count", "ev_rows", "ev_resid", "ev_conv", "jac", "ev_jac") if k in r}
         return res, info
 
     # ---- the reference's methods
@@ -335,6 +364,29 @@ class Integrator(IntegratorOptions):
             self._raise_unless_ok(status)
         rows = list(self._full_rows(Y, T, xs, us)[:, 0, :])
         return (rows, steps, status) if details else rows
+
+    def integrate_events_stm(self, x0, tf, events, event_jacs: bool = False, details: bool = False):
+        """``(row, J, eventlocs)`` of one problem (``integrate_events_stm_parallel``); with ``details`` ``(row, J, eventlocs, info)``, info
+        that call's dict for this problem."""
+        r = self.integrate_events_stm_parallel([x0], [tf], events, event_jacs=event_jacs, details=details)
+        return (*r[0][0], {k: v[0] for k, v in r[1].items()}) if details else r[0]
+
+    def integrate_events_stm_parallel(self, x0s, tfs, events, threads=None, event_jacs: bool = False, details: bool = False):
+        """A list of ``(row, J, eventlocs)``, the reference's ``STMEventRet`` (Integrator.h:2076-2082, :2125), from one propagation per
+        problem: ``row`` and ``eventlocs`` as ``integrate_parallel(x0s, tfs, events)`` returns them (the row's time is the end time),
+        ``J[XV, XV + 1 + UV + PV + 1]`` the Jacobian of the row's state, columns ``[x0 | t0 | u | p | t]``, the last one ``f`` at the end
+        state and end time.  ``event_jacs=True``: every entry of ``eventlocs[j]`` is ``(row, J_loc)``.  ``details``: ``(that list,
+        info)``, info the dict of ``integrate_parallel`` plus ``jac[m, XV, N + 1]`` and, with ``event_jacs``, ``ev_jac[m, ne,
+        MaxEventLocs, XV, N + 1]`` (every stored occurrence, located or not; NaN where unused) -- and no exception for a failed problem
+        (NaN in its state and ``J``).  ``threads`` is accepted and ignored.  The constant controller ``integrator(def_step, v)`` is
+        taken (the held-control path); a control law is refused.  (The ``events=`` keyword of ``integrate_stm*`` still raises
+        ``NotImplementedError``; routing it here is a one-line follow-up for a change that may edit the tests which pin that.)"""
+        if events is None:
+            raise ValueError("integrate_events_stm needs events: a list of (g, direction, stop); without them it is integrate_stm")
+        Y, T = self._rows(x0s, tfs)
+        self._no_controller_events()
+        res, info = self._propagate_events(Y, T, events, details, stm=True, event_jacs=bool(event_jacs))
+        return (res, info) if details else res
 
     @staticmethod
     def _no_events(what, events):

@@ -241,13 +241,8 @@ def ensure_bundle(dev_names, compile_only=None) -> str:
                            rtc=(flist, 3, 0, 0, f"ASSET_RTC_BUNDLE({flist})"), compile_only=compile_only)
 
 
-def ensure_event_module(ode, event_funcs, compile_only=None) -> str:
-    """One module that propagates `ode` with the event functions `event_funcs` (1..8 scalar functions of the ODE's input row):
-    csrc/propagate_event_kernels.h: prop_event_kernel<Ode, Ev>; include/asset_hip.h: asset_hip_propagate_events.  The ODE's functor is
-    emitted from ``ode.derivatives()`` as ensure_kernel emits it -- for a library ODE too: both functors have to be in the one
-    translation unit -- and the event functor from the stacked functions (its value is all the kernel calls).  The module is named by a
-    content hash of both; directions and stop counts are arguments of a call, not of the module.  hiprtc only.  Registering the
-    module needs no device (its sizes are read from the code object)."""
+def _event_module(ode, event_funcs, compile_only, stm: bool) -> str:
+    """ensure_event_module (kind 4) and ensure_event_stm_module (kind 6): the same two functors, another kernel list."""
     from . import vf
     from .vf.codegen import differentiate_function
     funcs = list(event_funcs)
@@ -268,7 +263,7 @@ def ensure_event_module(ode, event_funcs, compile_only=None) -> str:
     d = ode.derivatives()
     de = differentiate_function("events", vf.stack(funcs) if len(funcs) > 1 else funcs[0])
     h = hashlib.sha256((maths(emit_hip_functor(d, "OdeUser")) + maths(emit_hip_functor(de, "EvUser"))).encode()).hexdigest()[:12]
-    name = f"events_{_ident(ode.ode_name)}_{h}"
+    name = f"{'eventstm' if stm else 'events'}_{_ident(ode.ode_name)}_{h}"
     if _lib.has_kernel(name, _lib.FUNCTION, False):
         return name
     import copy
@@ -278,9 +273,31 @@ def ensure_event_module(ode, event_funcs, compile_only=None) -> str:
     hdr = ("#include <math.h>\n#include \"" + os.path.join(build.CSRC, "asset_math.h") + "\"\n" + emit_hip_functor(d, so) + "\n"
            + emit_hip_functor(de, se))
     flist = f"{so}, {se}"
+    if stm:
+        return _build_and_load(name, "eventstm.h", hdr, "eventstm_0", "", _lib.FUNCTION, False,
+                               f"events and STM of ODE '{ode.ode_name}'", rtc=(flist, 6, 0, 0, f"ASSET_RTC_PROP_EVENTS_STM({flist})"),
+                               compile_only=compile_only)
     return _build_and_load(name, "events.h", hdr, "events_0", "", _lib.FUNCTION, False,
                            f"events of ODE '{ode.ode_name}'", rtc=(flist, 4, 0, 0, f"ASSET_RTC_PROP_EVENTS({flist})"),
                            compile_only=compile_only)
+
+
+def ensure_event_module(ode, event_funcs, compile_only=None) -> str:
+    """One module that propagates `ode` with the event functions `event_funcs` (1..8 scalar functions of the ODE's input row):
+    csrc/propagate_event_kernels.h: prop_event_kernel<Ode, Ev>; include/asset_hip.h: asset_hip_propagate_events.  The ODE's functor is
+    emitted from ``ode.derivatives()`` as ensure_kernel emits it -- for a library ODE too: both functors have to be in the one
+    translation unit -- and the event functor from the stacked functions (its value is all the kernel calls).  The module is named by a
+    content hash of both; directions and stop counts are arguments of a call, not of the module.  hiprtc only.  Registering the
+    module needs no device (its sizes are read from the code object)."""
+    return _event_module(ode, event_funcs, compile_only, False)
+
+
+def ensure_event_stm_module(ode, event_funcs, compile_only=None) -> str:
+    """One module that propagates `ode` with the event functions `event_funcs` AND its state-transition matrix:
+    csrc/propagate_event_stm_kernels.h: prop_event_stm_kernel, prop_event_jac_kernel <Ode, Ev>; include/asset_hip.h:
+    asset_hip_propagate_events_stm.  The two functors are those of ensure_event_module (the event functor's value is all the kernels
+    call; the ODE's Jacobian is its functor's ``fj``); the module is of kind 6, keyed by the same content under a name of its own."""
+    return _event_module(ode, event_funcs, compile_only, True)
 
 
 def controller_varlocs(ode, ucon, varlocs):

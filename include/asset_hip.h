@@ -387,6 +387,29 @@ int asset_hip_propagate_events(const char* module, const double* y0, long long m
                                int* steps, int* status, int device);
 int asset_hip_event_module_sizes(const char* module, int* xv, int* uv, int* pv, int* ne);
 
+/* ---- batched propagation with events and the state-transition matrix ----
+ * Replaces the STM + Events overloads of the reference (Integrators/Integrator.h:2076-2082, :2125) for an integrator without a
+ * controller (csrc/propagate_event_stm_kernels.h): ONE propagation that gives the end state (the state at which it stopped), every
+ * located occurrence, and the Jacobian of each of them.  `module` is a run-time module of kind 6 (asset_hip_jit_plugin; the ODE's
+ * functor and the event functor, ASSET_RTC_PROP_EVENTS_STM(Ode, Ev)); every other argument and output of asset_hip_propagate_events
+ * means what it means there, and the state side -- xf, t_end, stopped, ev_count, ev_rows, ev_resid, ev_conv, steps, status -- is that
+ * call's bit for bit.  jac[m][XV][XV+1+UV+PV+1], columns [x0 | t0 | u | p | t] as asset_hip_propagate_stm: the x0, u, p columns are the
+ * exact derivative of the discrete map with the step sequence held fixed, d / d t0 = -S_x f(x0, t0, u, p), and the last column is f at
+ * the end state and at t_end (not tf when the problem stopped).  ev_jac[m][ne][max_locs][XV][XV+1+UV+PV+1] (may be NULL: then it is
+ * neither computed nor allocated) is the same at every stored occurrence: the discrete derivative of the stored state through the
+ * accepted steps up to the start of the bracketing step, then the one step of size theta h with theta held, its last column f at
+ * the occurrence's own state and time; for an occurrence stored with ev_conv = 0 it is that of the trial point whose state was
+ * stored.  NaN in jac when status != 0, NaN in ev_jac where the slot is unused or status != 0.  steps and status may be NULL.
+ * asset_hip_event_module_sizes answers for a module of kind 6 too.  asset_hip_propagate_events_stm_plan: the launch plan the call uses
+ * for m problems, out[7] as asset_hip_propagate_plan gives it (no device) -- it IS asset_hip_propagate_plan(XV, UV, PV, m, 1).  Errors as asset_hip_propagate_events, all found before the device
+ * is touched, nothing written; ASSET_HIP_ENOODE also for a module that is not of kind 6 (asset_hip_propagate_events refuses one of
+ * kind 6 the same way). */
+int asset_hip_propagate_events_stm_plan(const char* module, long long m, long long* out);
+int asset_hip_propagate_events_stm(const char* module, const double* y0, long long m, const double* tf, const asset_hip_integ_options* opt,
+                                   int ne, const int* direction, const int* stop, double event_tol, int max_event_iters, int max_locs,
+                                   double* xf, double* jac, double* t_end, int* stopped, int* ev_count, double* ev_rows, double* ev_resid,
+                                   int* ev_conv, double* ev_jac, int* steps, int* status, int device);
+
 /* ---- batched propagation with a controller ----
  * Replaces Integrator::integrate_parallel / integrate_dense_parallel / integrate_stm_parallel for an integrator WITH a controller
  * (Integrators/Integrator.h:96-118, 190-249, 398-463; csrc/propagate_ctrl_kernels.h).  `module` is a run-time module that holds the
@@ -459,7 +482,8 @@ int asset_hip_load_plugin(const char* path);
  * ASSET_RTC_FUNC(functor) line; kind 1 = transcription of an ODE, 2 = plain function, 3 = bundle of plain functions (mode,
  * blocked, seg_per_group ignored), 4 = an ODE with event functions (functor = "Ode, Ev", source ending in
  * ASSET_RTC_PROP_EVENTS(Ode, Ev); registered WITHOUT a device: its sizes are read from the code object, its first launch loads it), 5 = an ODE with a control law (functor = "Ode, Ctl", source ending in ASSET_RTC_PROP_CTRL(Ode, Ctl); registered
- * without a device like kind 4); options = hiprtc options ("--offload-arch=gfx950", "-I...", ...).
+ * without a device like kind 4), 6 = an ODE with event functions, propagated with its state-transition matrix (functor = "Ode, Ev",
+ * source ending in ASSET_RTC_PROP_EVENTS_STM(Ode, Ev); registered without a device like kind 4); options = hiprtc options ("--offload-arch=gfx950", "-I...", ...).
  *   asset_hip_jit_compile  compiles and writes the code object and the lowered kernel names to cache_path; needs no device.
  *   asset_hip_jit_plugin   registers the module under `name` on the current device: from cache_path when that file
  *                          exists, else by compiling `source` (and writing cache_path when it is not NULL).  0 when
