@@ -845,7 +845,17 @@ __device__ __forceinline__ void lgl_resident_body(const EvalArgs& a) {
   if constexpr (LOOP) asm volatile("" : "+v"(lane));
   const int lr = lane & 15, lk = lane >> 4;
   RTS();
-  auto slot_dma = [&](int slot, int seg_) {             // slot <- the workspace's slot of mesh segment seg_ (WSLOTD doubles)
+  // entry `l` of the x_AUX rows (1 - s_i, s_i, 0, 1 for i = l / 4): the K values s_i are compile-time entries of the constant table,
+  // picked by lane with selects.  (Read as ctab.s[l >> 2] it was a vector load from the table behind the gather's trip to memory,
+  // once per region: two more waits, one behind the other -- DESIGN 4.0d)
+  auto aux_row = [&](int l) -> double {
+    const int i = l >> 2, wq = l & 3;
+    double si = ctab.s[0];
+#pragma unroll
+    for (int k = 1; k < K; k++) si = (i == k) ? ctab.s[k] : si;
+    return wq == 0 ? 1.0 - si : (wq == 1 ? si : (wq == 3 ? 1.0 : 0.0));
+  };
+  auto slot_dma = [&](int slot, int seg_) {            // slot <- the workspace's slot of mesh segment seg_ (WSLOTD doubles)
     const void* src = a.work + size_t(__builtin_amdgcn_readfirstlane(seg_)) * D::WSLOT;
     const unsigned dst = __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)(slots + slot * SLOT));
     constexpr int ROWS = D::WSLOTD * 2 / 64, TAIL = D::WSLOTD * 2 % 64;
@@ -891,10 +901,7 @@ __device__ __forceinline__ void lgl_resident_body(const EvalArgs& a) {
 #pragma unroll
     for (int t = 0; t < NTAB; t++)
       if (lane + 64 * t < D::TABSZ) tabL[lane + 64 * t] = tabv[t];
-    if (lane < 4 * K) {
-      const int i = lane >> 2, w = lane & 3;
-      xtra[R::x_AUX + lane] = w == 0 ? 1.0 - ctab.s[i] : (w == 1 ? ctab.s[i] : (w == 3 ? 1.0 : 0.0));
-    }
+    if (lane < 4 * K) xtra[R::x_AUX + lane] = aux_row(lane);
     if (lane < GR) slots[lane * SLOT + R::s_Z0] = 0.0;
     if (lane < 4) xtra[R::x_Z4 + lane] = 0.0;
   } else {
@@ -944,6 +951,7 @@ __device__ __forceinline__ void lgl_resident_body(const EvalArgs& a) {
 #pragma unroll
     for (int t = 0; t < NTAB; t++)
       tabv[t] = (lane + 64 * t < D::TABSZ) ? reinterpret_cast<const double*>(&d_lgl_tab[D::TAB])[lane + 64 * t] : 0.0;
+    const double auxv = aux_row(lane);   // (once, for every region: no load behind the trip of X, L and the tables)
 #pragma unroll
     for (int w = 0; w < NWV; w++) {      // every region of the workgroup: tables, constant rows, zero cells
       lds_double* const tb = PAIR ? region0 + w * R::REGION : tabL;
@@ -951,10 +959,7 @@ __device__ __forceinline__ void lgl_resident_body(const EvalArgs& a) {
 #pragma unroll
       for (int t = 0; t < NTAB; t++)
         if (lane + 64 * t < D::TABSZ) tb[lane + 64 * t] = tabv[t];
-      if (lane < 4 * K) {
-        const int i = lane >> 2, wq = lane & 3;
-        xt[R::x_AUX + lane] = wq == 0 ? 1.0 - ctab.s[i] : (wq == 1 ? ctab.s[i] : (wq == 3 ? 1.0 : 0.0));
-      }
+      if (lane < 4 * K) xt[R::x_AUX + lane] = auxv;
       if (lane < GR) tb[D::TABSZ + lane * SLOT + R::s_Z0] = 0.0;
       if (lane < 4) xt[R::x_Z4 + lane] = 0.0;
       if (grp == 0 && lane == 0) xt[R::x_FLAG] = 0.0;
