@@ -83,8 +83,10 @@ inline int build_kkt_map(int IR, int OR, bool plain_function, int nseg, const in
       else {
         const unsigned char u = uses[size_t(m - lo)];
         if (u == 1) enc[i] = m;
-        else if (!staged(i) || !multi_of.count(m)) enc[i] = -(m + 2);   // (a location staged for its Hessian slots takes no other)
-        else enc[i] = -(int32_t(nvalues) + fill[multi_of[m]]++ + 2);
+        else if (staged(i)) enc[i] = -(int32_t(nvalues) + fill[multi_of[m]]++ + 2);
+        else if (multi_of.count(m))   // (asm_reduce_kernel ASSIGNS the staged sum: an add into the same location would be lost)
+          return fail(ASSET_HIP_EINVAL, "a Jacobian slot names a location that is staged for three or more Hessian slots");
+        else enc[i] = -(m + 2);
       }
     }
   }

@@ -241,7 +241,7 @@ int asset_hip_host_unregister(void* ptr);
  * more do (entries between phase parameters: one contribution per segment), through staging cells that are summed in
  * slot order after the kernel, so the assembled values are bitwise repeatable -- the device array must hold zeros at
  * this constraint's locations on entry and then holds the constraint's contributions.  accumulate = 1: every slot is added atomically, a true += into whatever the array
- * holds (about 2x the evaluation time).
+ * holds (about 2x the evaluation time).  Precondition (accumulate = 0): a location three or more Hessian slots share is named by no Jacobian slot -- ASSET_HIP_EINVAL otherwise.
  * asset_hip_defect_eval_assembled: host pointers; FX / AGX blocks as in asset_hip_defect_eval; kkt_values[nvalues] is
  * ACCUMULATED into (the caller zeroes it per evaluation, PSIOPT.cpp:107) -- the contributions are summed in a zeroed
  * device array first, then the contiguous range of locations this constraint touches crosses PCIe and is added.

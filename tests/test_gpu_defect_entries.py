@@ -8,7 +8,8 @@ tests/golden/defect_entries/, made by tests/golden/make_golden_defect_entries.py
   pi(s) -- a fixed pseudo-random map in which no two neighbours are equal -- and every block of every segment is checked.  n comes
   from the launch planner: for each distinct sequence of kernel slot names (and XCD placement of the unit stage) up to 32 768
   segments the smallest size that plans it, that size minus one and a size that leaves a ragged last group;
-* the assembled path at one size: the values of eval_assembled against the scatter of the blocks just checked.
+* the assembled path at one size: the values of eval_assembled against the scatter of the blocks just checked (every other size, kernel
+  and map: tests/test_gpu_assembled_entries.py).
 
 On a 256-CU device the planner reaches every form of the tiled shapes at or below 24 577 segments (the last: K_RESL2 of
 Reentry-Trapezoidal), so none is left to test_gpu_parity.py: test_launch_form_boundaries alone; on a device with more compute units a
@@ -122,14 +123,14 @@ def test_every_shape_every_kind(shape):
 
 
 @functools.lru_cache(maxsize=None)
-def planned_forms(name, mode, blocked, cus, what=JAC_ADJGRAD_HESS, max_nseg=MAX_NSEG):
-    """{form: [sizes]} from the planner: form = (kernel slot names ..., XCD placement of the unit stage); sizes = the smallest that
+def planned_forms(name, mode, blocked, cus, what=JAC_ADJGRAD_HESS, max_nseg=MAX_NSEG, assembled=False):
+    """{form: [sizes]} from the planner (``assembled``: of the evaluation into a value array, tests/test_gpu_assembled_entries.py): form = (kernel slot names ..., XCD placement of the unit stage); sizes = the smallest that
     plans it, that size minus one, one that is no multiple of the plan's group -- the segments per group of a unit stage, else the
     number of workgroups the mesh is split over -- (the first with more than two groups of it where the form has such a size)."""
     first, group_of = {}, {}
     order = []
     for n in range(1, max_nseg + 1):
-        steps, units_gp = _lib.launch_plan(name, _lib.MODES[mode], blocked, what, False, n, cus=cus)
+        steps, units_gp = _lib.launch_plan(name, _lib.MODES[mode], blocked, what, assembled, n, cus=cus)
         form = tuple(s[0] for s in steps) + (("xcd",) if units_gp > 0 else ())
         if form not in first:
             first[form] = n
@@ -210,8 +211,9 @@ def test_assembled_values_are_the_scatter_of_the_checked_blocks(oracle):
     many segments, so many blocks add into one Hessian location in an order that is not known: within 4 u sum |contributions| per
     location; bit for bit where a location takes one.  Every segment keeps constraint rows of its own, as the defects of a phase
     do: a Jacobian location then takes one contribution (the map builder adds the slots of a shared Jacobian location atomically,
-    one after the other, and 439 terms in an unknown order are only held by 438 u sum |c|: 26 x 4 u sum |c| with shared rows on that device, so many-way Jacobian sums are left to
-    tests/test_gpu_assembly.py)."""
+    one after the other, and 439 terms in an unknown order are only held by 438 u sum |c|: 26 x 4 u sum |c| with shared rows on that device.  What this test
+    leaves open -- the other assembly kernels, shared locations held harder than 4 u sum |c|, many-way Jacobian sums, the staged
+    reduction, the RHS gathers -- is held per location by tests/test_gpu_assembled_entries.py)."""
     shape = ("reentry", "LGL7", False)
     f = dc.load(shape)
     cus = device_cus()

@@ -122,3 +122,10 @@ def test_kkt_map_query_refusals(oracle):
     _lib.kkt_map(ir, orr, False, locs, fits + 1, accumulate=True)          # (no staging in accumulate mode: nothing to overflow)
     with pytest.raises(_lib.AssetHipError, match="bad kkt map arguments"):
         _lib.kkt_map(ir, orr, False, locs, 0)
+    # a Jacobian slot at a location that is staged for its Hessian slots: the reduction ASSIGNS the staged sum, the add would be lost
+    staged_loc = _lib.kkt_map(ir, orr, False, locs, nvalues)[2][0]
+    bad = locs.copy()
+    bad[2, ir] = staged_loc                                                # (slot IR of a block: J(0, 0), behind the IR Hessian slots of column 0)
+    with pytest.raises(_lib.AssetHipError, match=r"rc=-1\).*Jacobian slot names a location that is staged"):
+        _lib.kkt_map(ir, orr, False, bad, nvalues)
+    _lib.kkt_map(ir, orr, False, bad, nvalues, accumulate=True)            # (every slot an add: nothing is assigned)
