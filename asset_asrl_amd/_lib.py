@@ -17,6 +17,8 @@ FUNCTION, TRAPEZOIDAL, LGL3, LGL5, LGL7 = 0, 1, 2, 3, 4
 MODES = {"Function": FUNCTION, "Trapezoidal": TRAPEZOIDAL, "LGL3": LGL3, "LGL5": LGL5, "LGL7": LGL7}
 CON, CON_ADJGRAD, JAC, JAC_ADJGRAD, JAC_ADJGRAD_HESS = range(5)
 KEEP_HESSIAN_SLOTS = 0x100   # OR into JAC / JAC_ADJGRAD: Hessian slots of the blocks left untouched (include/asset_hip.h)
+# the kinds of a compiled module (csrc/kernel_meta.h: MF_KIND; the integers are ABI -- asset_hip_jit_plugin's `kind`, meta[0] of a module)
+KIND_LGL, KIND_FUNCTION, KIND_BUNDLE, KIND_EVENTS, KIND_CTRL, KIND_EVENTS_STM = range(1, 7)
 
 _dp = C.POINTER(C.c_double)
 _ip = C.POINTER(C.c_int32)

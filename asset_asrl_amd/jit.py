@@ -51,6 +51,11 @@ def _ident(s: str) -> str:
     return re.sub(r"[^0-9a-zA-Z_]", "_", s)
 
 
+def _maths(text: str) -> str:
+    """The lines of a generated functor that enter a content hash: the names do not, the maths does."""
+    return "\n".join(ln for ln in text.splitlines() if "name()" not in ln and not ln.startswith("// generated"))
+
+
 def device_name(ode) -> str:
     """Name the ODE is registered under on the device: library ODEs keep theirs, user ODEs get a content hash."""
     from .ode import ODE_LIBRARY
@@ -59,9 +64,7 @@ def device_name(ode) -> str:
     cached = getattr(ode, "_device_name", None)
     if cached:
         return cached
-    body = emit_hip_functor(ode.derivatives(), "OdeUser")       # the name does not enter the hash, the maths does
-    body = "\n".join(ln for ln in body.splitlines() if "name()" not in ln and not ln.startswith("// generated"))
-    h = hashlib.sha256(body.encode()).hexdigest()[:10]
+    h = hashlib.sha256(_maths(emit_hip_functor(ode.derivatives(), "OdeUser")).encode()).hexdigest()[:10]
     ode._device_name = f"{_ident(ode.ode_name)}_{h}"
     return ode._device_name
 
@@ -98,7 +101,7 @@ def ensure_kernel(ode, mode: str, blocked: bool, compile_only=None) -> str:
     tag = f"{mode.lower()}_{int(blocked)}"
     cs_id = 1 if mode == "Trapezoidal" else _MODE_CS[mode]
     return _build_and_load(name, "ode.h", hdr, tag, reg.replace("{S}", sname), mode_id, blocked,
-                           f"user ODE '{ode.ode_name}'", rtc=(sname, 1, cs_id, G, f"ASSET_RTC_LGL({sname}, {cs_id}, {int(blocked)}, {G})"),
+                           f"user ODE '{ode.ode_name}'", rtc=(sname, _lib.KIND_LGL, cs_id, G, f"ASSET_RTC_LGL({sname}, {cs_id}, {int(blocked)}, {G})"),
                            compile_only=compile_only)
 
 
@@ -201,9 +204,7 @@ def ensure_function(func, name: str, compile_only=None) -> str:
     defect -- FX / AGX blocks and the KKT block (Jacobian + lower-triangle adjoint Hessian) of every application."""
     from .vf.codegen import differentiate_function
     d = differentiate_function(name, func)
-    body = emit_hip_functor(d, "FnUser")
-    body = "\n".join(ln for ln in body.splitlines() if "name()" not in ln and not ln.startswith("// generated"))
-    dev = f"{_ident(name)}_{hashlib.sha256(body.encode()).hexdigest()[:10]}"
+    dev = f"{_ident(name)}_{hashlib.sha256(_maths(emit_hip_functor(d, 'FnUser')).encode()).hexdigest()[:10]}"
     d.name = dev
     sname = "Fn_" + _ident(dev)
     _FUNCTORS[dev] = (sname, d)                 # (a bundle is assembled from the functors of its members: ensure_bundle)
@@ -212,7 +213,7 @@ def ensure_function(func, name: str, compile_only=None) -> str:
     hdr = ("#pragma once\n#include <math.h>\n#include \"" + os.path.join(build.CSRC, "asset_math.h") + "\"\n"
            + emit_hip_functor(d, sname))
     return _build_and_load(dev, "fn.h", hdr, "function_0", f"ASSET_REGISTER_FUNC({sname})", _lib.FUNCTION, False,
-                           f"function '{name}'", rtc=(sname, 2, 0, 0, f"ASSET_RTC_FUNC({sname})"), compile_only=compile_only)
+                           f"function '{name}'", rtc=(sname, _lib.KIND_FUNCTION, 0, 0, f"ASSET_RTC_FUNC({sname})"), compile_only=compile_only)
 
 
 def ensure_bundle(dev_names, compile_only=None) -> str:
@@ -238,13 +239,34 @@ def ensure_bundle(dev_names, compile_only=None) -> str:
     hdr = ("#include <math.h>\n#include \"" + os.path.join(build.CSRC, "asset_math.h") + "\"\n" + "\n".join(body))
     flist = ", ".join(snames)
     return _build_and_load(name, "bundle.h", hdr, "bundle_0", "", _lib.FUNCTION, False, f"bundle of {len(dev_names)} functions",
-                           rtc=(flist, 3, 0, 0, f"ASSET_RTC_BUNDLE({flist})"), compile_only=compile_only)
+                           rtc=(flist, _lib.KIND_BUNDLE, 0, 0, f"ASSET_RTC_BUNDLE({flist})"), compile_only=compile_only)
+
+
+def _pair_module(ode, second, second_user, second_prefix, kind, prefix, hdr_name, tag, macro, what, compile_only) -> str:
+    """One module of `ode` and a second function (its stacked events, its control law) -- the module kinds of two functors: both
+    are emitted into the one translation unit, and the module is named `prefix`_<ode>_<content hash of both>.  `second_user` names the
+    second functor inside the hash, `second_prefix` its struct; `macro` is the ASSET_RTC_* line the source ends in (csrc/rtc_device.h)."""
+    from .vf.codegen import differentiate_function
+    d = ode.derivatives()
+    d2 = differentiate_function(second[0], second[1])
+    h = hashlib.sha256((_maths(emit_hip_functor(d, "OdeUser")) + _maths(emit_hip_functor(d2, second_user))).encode()).hexdigest()[:12]
+    name = f"{prefix}_{_ident(ode.ode_name)}_{h}"
+    if _lib.has_kernel(name, _lib.FUNCTION, False):
+        return name
+    import copy
+    d = copy.copy(d)                                # (the ODE keeps its own record: only the copy is renamed)
+    d.name, d2.name = device_name(ode), name
+    so, s2 = "Ode_" + _ident(d.name), second_prefix + _ident(name)
+    hdr = ("#include <math.h>\n#include \"" + os.path.join(build.CSRC, "asset_math.h") + "\"\n" + emit_hip_functor(d, so) + "\n"
+           + emit_hip_functor(d2, s2))
+    flist = f"{so}, {s2}"
+    return _build_and_load(name, hdr_name, hdr, tag, "", _lib.FUNCTION, False, f"{what} of ODE '{ode.ode_name}'",
+                           rtc=(flist, kind, 0, 0, f"{macro}({flist})"), compile_only=compile_only)
 
 
 def _event_module(ode, event_funcs, compile_only, stm: bool) -> str:
-    """ensure_event_module (kind 4) and ensure_event_stm_module (kind 6): the same two functors, another kernel list."""
+    """ensure_event_module (KIND_EVENTS) and ensure_event_stm_module (KIND_EVENTS_STM): the same two functors, another kernel list."""
     from . import vf
-    from .vf.codegen import differentiate_function
     funcs = list(event_funcs)
     if not 1 <= len(funcs) <= 8:
         raise ValueError("an event module holds 1..8 event functions")
@@ -256,30 +278,12 @@ def _event_module(ode, event_funcs, compile_only, stm: bool) -> str:
             raise ValueError(f"event {j} has {g.IRows()} inputs, the ODE's rows have {N}")
         if g.ORows() != 1:
             raise ValueError(f"event {j} is not a scalar function ({g.ORows()} outputs)")
-
-    def maths(text):                                # (the names do not enter the hash, the maths does)
-        return "\n".join(ln for ln in text.splitlines() if "name()" not in ln and not ln.startswith("// generated"))
-
-    d = ode.derivatives()
-    de = differentiate_function("events", vf.stack(funcs) if len(funcs) > 1 else funcs[0])
-    h = hashlib.sha256((maths(emit_hip_functor(d, "OdeUser")) + maths(emit_hip_functor(de, "EvUser"))).encode()).hexdigest()[:12]
-    name = f"{'eventstm' if stm else 'events'}_{_ident(ode.ode_name)}_{h}"
-    if _lib.has_kernel(name, _lib.FUNCTION, False):
-        return name
-    import copy
-    d = copy.copy(d)                                # (the ODE keeps its own record: only the copy is renamed)
-    d.name, de.name = device_name(ode), name
-    so, se = "Ode_" + _ident(d.name), "Ev_" + _ident(name)
-    hdr = ("#include <math.h>\n#include \"" + os.path.join(build.CSRC, "asset_math.h") + "\"\n" + emit_hip_functor(d, so) + "\n"
-           + emit_hip_functor(de, se))
-    flist = f"{so}, {se}"
+    second = ("events", vf.stack(funcs) if len(funcs) > 1 else funcs[0])
     if stm:
-        return _build_and_load(name, "eventstm.h", hdr, "eventstm_0", "", _lib.FUNCTION, False,
-                               f"events and STM of ODE '{ode.ode_name}'", rtc=(flist, 6, 0, 0, f"ASSET_RTC_PROP_EVENTS_STM({flist})"),
-                               compile_only=compile_only)
-    return _build_and_load(name, "events.h", hdr, "events_0", "", _lib.FUNCTION, False,
-                           f"events of ODE '{ode.ode_name}'", rtc=(flist, 4, 0, 0, f"ASSET_RTC_PROP_EVENTS({flist})"),
-                           compile_only=compile_only)
+        return _pair_module(ode, second, "EvUser", "Ev_", _lib.KIND_EVENTS_STM, "eventstm", "eventstm.h", "eventstm_0",
+                            "ASSET_RTC_PROP_EVENTS_STM", "events and STM", compile_only)
+    return _pair_module(ode, second, "EvUser", "Ev_", _lib.KIND_EVENTS, "events", "events.h", "events_0", "ASSET_RTC_PROP_EVENTS",
+                        "events", compile_only)
 
 
 def ensure_event_module(ode, event_funcs, compile_only=None) -> str:
@@ -296,7 +300,7 @@ def ensure_event_stm_module(ode, event_funcs, compile_only=None) -> str:
     """One module that propagates `ode` with the event functions `event_funcs` AND its state-transition matrix:
     csrc/propagate_event_stm_kernels.h: prop_event_stm_kernel, prop_event_jac_kernel <Ode, Ev>; include/asset_hip.h:
     asset_hip_propagate_events_stm.  The two functors are those of ensure_event_module (the event functor's value is all the kernels
-    call; the ODE's Jacobian is its functor's ``fj``); the module is of kind 6, keyed by the same content under a name of its own."""
+    call; the ODE's Jacobian is its functor's ``fj``); the module is of KIND_EVENTS_STM, keyed by the same content under a name of its own."""
     return _event_module(ode, event_funcs, compile_only, True)
 
 
@@ -334,33 +338,14 @@ def ensure_controller_module(ode, ucon, varlocs, compile_only=None) -> str:
     `varlocs` from the ODE's input row, so it is a function of the FULL row and `varlocs` are compile-time content of the module.  The
     module is named by a content hash of both functors.  hiprtc only.  Registering the module needs no device."""
     from . import vf
-    from .vf.codegen import differentiate_function
     locs = controller_varlocs(ode, ucon, varlocs)
     if jit_route() != "hiprtc":
         raise _lib.AssetHipError("controller modules are compiled in process (unset ASSET_HIP_JIT=hipcc)")
     N = ode.XVars() + 1 + ode.UVars() + ode.PVars()
     row = vf.Arguments(N)
     law = ucon.eval(vf.stack([row[v] for v in locs]) if len(locs) > 1 else row[locs[0]])
-
-    def maths(text):                                # (the names do not enter the hash, the maths does)
-        return "\n".join(ln for ln in text.splitlines() if "name()" not in ln and not ln.startswith("// generated"))
-
-    d = ode.derivatives()
-    dc = differentiate_function("controller", law)
-    h = hashlib.sha256((maths(emit_hip_functor(d, "OdeUser")) + maths(emit_hip_functor(dc, "CtlUser"))).encode()).hexdigest()[:12]
-    name = f"ctrl_{_ident(ode.ode_name)}_{h}"
-    if _lib.has_kernel(name, _lib.FUNCTION, False):
-        return name
-    import copy
-    d = copy.copy(d)                                # (the ODE keeps its own record: only the copy is renamed)
-    d.name, dc.name = device_name(ode), name
-    so, sc = "Ode_" + _ident(d.name), "Ctl_" + _ident(name)
-    hdr = ("#include <math.h>\n#include \"" + os.path.join(build.CSRC, "asset_math.h") + "\"\n" + emit_hip_functor(d, so) + "\n"
-           + emit_hip_functor(dc, sc))
-    flist = f"{so}, {sc}"
-    return _build_and_load(name, "controller.h", hdr, "ctrl_0", "", _lib.FUNCTION, False,
-                           f"controller of ODE '{ode.ode_name}'", rtc=(flist, 5, 0, 0, f"ASSET_RTC_PROP_CTRL({flist})"),
-                           compile_only=compile_only)
+    return _pair_module(ode, ("controller", law), "CtlUser", "Ctl_", _lib.KIND_CTRL, "ctrl", "controller.h", "ctrl_0", "ASSET_RTC_PROP_CTRL",
+                        "controller", compile_only)
 
 
 def prune_unused(verbose: bool = False, everything: bool = False) -> int:
