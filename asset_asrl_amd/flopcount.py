@@ -64,7 +64,7 @@ def sparse_useful_flops(derivs, cs: int, blocked: bool = False) -> Dict[str, int
             yc, cnode = ycol(c)
             fma += (2 * K + colJ[yc]) if cnode else cs * colJ[yc]
     fma += OR * (2 * cs + 1)                                 # the defect values
-    ode_ops = derivs.stats()["ops_fjgh"]
+    ode_ops = derivs.stats()["ops_fjgh"]                     # (a root node: iters x its template, an upper bound -- vf/ir.py: count_ops)
     algebra = 2 * fma
     return {"algebra": algebra, "ode": (cs + K) * ode_ops, "total": algebra + (cs + K) * ode_ops, "IR": IR, "OR": OR,
             "dense_survey": survey_dense_flops(n, m, p, cs, ode_ops)}

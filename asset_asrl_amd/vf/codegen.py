@@ -28,7 +28,7 @@ from typing import Dict, List, Sequence, Tuple
 from .functions import VectorFunction
 import numpy as np
 
-from .ir import COND_OPS, TABLES, tab_array
+from .ir import COND_OPS, ROOTS, TABLES, count_ops, tab_array, with_templates
 from .ir import GRAPH as G
 from .ir import Node, topo_order
 
@@ -52,8 +52,7 @@ class OdeDerivatives:
         return self.xv + 1 + self.uv + self.pv
 
     def stats(self) -> Dict[str, int]:
-        def count(roots):
-            return sum(1 for n in topo_order(roots) if n.args)
+        count = count_ops           # (a root: iters x its template, an upper bound -- ir.count_ops)
         z = G.zero
         return {
             "ops_f": count(self.f),
@@ -72,8 +71,7 @@ def differentiate_function(name: str, func: VectorFunction) -> OdeDerivatives:
     return differentiate(name, func, func.ORows(), func.IRows() - func.ORows() - 1, 0)
 
 
-def _count_ops(roots) -> int:
-    return sum(1 for n in topo_order(roots) if n.args)
+_count_ops = count_ops
 
 
 def _differentiate_flat(f, ys, lams):
@@ -491,8 +489,10 @@ class _Printer:
     unless needed elsewhere).  ``pair_sincos``: emit one ``sincos`` for a sin/cos pair on the same argument (device)."""
 
     def __init__(self, roots: Sequence[Node], yname="y{}", lname="l{}", loaded=None, pair_sincos=False,
-                 level_order=False, tabprefix=""):
+                 level_order=False, tabprefix="", varnames=None, tprefix=""):
         self.tabprefix = tabprefix           # plain C: the table arrays and look-ups are file-scope names of this function's own
+        self.varnames = varnames             # the template of a root inside its loop: {input: the expression it stands for}
+        self.tprefix = tprefix               # ... and its temporaries carry the loop's name in front
         self.names: Dict[int, str] = {}
         self.lines: List[str] = []
         self.used_y = set()
@@ -537,24 +537,57 @@ class _Printer:
                 continue
             if n.op in COND_OPS:             # a condition is printed where it is used (inside its select): no temporary of its own
                 continue
+            if n.op == "root":               # one bounded loop, in front of the node's first use
+                self._emit_root(n)
+                continue
             if n.id in partner:
                 other = partner[n.id]
                 k = len(self.lines)
-                sn, cn = f"t{k}s", f"t{k}c"
+                sn, cn = f"{tprefix}t{k}s", f"{tprefix}t{k}c"
                 self.lines.append(f"double {sn}, {cn}; asset_sincos({self.ref(n.args[0])}, &{sn}, &{cn});{fence}")
                 self.names[n.id] = sn if n.op == "sin" else cn
                 self.names[other.id] = cn if n.op == "sin" else sn
                 self.pos[n.id] = self.pos[other.id] = len(self.lines) - 1
                 continue
-            nm = f"t{len(self.lines)}"
+            nm = f"{tprefix}t{len(self.lines)}"
             self.lines.append(f"const double {nm} = {self._expr(n)};{fence if n.op in TRANSCENDENTAL else ''}")
             self.names[n.id] = nm
             self.pos[n.id] = len(self.lines) - 1
+
+    def _emit_root(self, n: Node):
+        """The iteration of a root node (ir.RootTemplate.solve is the same rule in Python) as ONE statement of the schedule: the
+        loop-carried iterate is a plain local, everything behind the loop sees its final value.  The template's statements live
+        inside the loop -- those of the residual in front of the test, those only the step needs behind it -- under names of the
+        loop's own.  ``unroll 1``: `iters` copies of the template would be larger than the rest of most bodies.  A lane leaves at
+        the trip ITS residual meets the tolerance (the host's rule: no cross-lane test); the trip count is bounded by `iters`
+        whatever the data, and a zero step derivative gives that lane Inf / NaN and nothing else."""
+        tpl = ROOTS[n.value]
+        nm = f"{self.tprefix}r{len(self.lines)}"
+        names = {0: nm}
+        names.update({i: self.ref(a) for i, a in enumerate(n.args) if i > 0})
+        F, D = lower_reciprocals([tpl.F, tpl.D])
+        p = _Printer([F, D], pair_sincos=self.device_math, tabprefix=self.tabprefix, varnames=names, tprefix=nm + "_")
+        self.used_c |= p.used_c
+        cut = p.pos.get(F.id, -1) + 1        # (depth-first from [F, D]: the lines up to F's own are the residual's)
+        txt = [f"double {nm} = {self.ref(n.args[0])};"]
+        if self.device_math:
+            txt.append("#pragma unroll 1")
+        txt.append(f"for (int {nm}_i = 0; {nm}_i < {tpl.iters}; ++{nm}_i) {{")
+        txt += ["  " + ln for ln in p.lines[:cut]]
+        txt.append(f"  if (fabs({p.ref(F)}) < {_cnum(tpl.tol)}) break;")
+        txt += ["  " + ln for ln in p.lines[cut:]]
+        txt.append(f"  {nm} -= {p.ref(F)} / {p.ref(D)};")
+        txt.append("}")
+        self.lines.append(("\n    " if self.device_math else "\n  ").join(txt))     # (one entry of the schedule, printed at the body's indent)
+        self.names[n.id] = nm
+        self.pos[n.id] = len(self.lines) - 1
 
     def ref(self, n: Node) -> str:
         if n.op == "const":
             return _cnum(n.value)
         if n.op == "var":
+            if self.varnames is not None:
+                return self.varnames[n.value]
             return self.yname.format(n.value)
         if n.op == "lam":
             return self.lname.format(n.value)
@@ -606,7 +639,7 @@ class _Printer:
 def table_arrays(roots: Sequence[Node]) -> List[Tuple[str, List[float]]]:
     """[(array name, numbers)] of every table array the expressions read (sorted: the same function prints the same code)."""
     need = set()
-    for n in topo_order(roots):
+    for n in with_templates(roots):              # (the template of a root may read a table)
         if n.op == "tabget":
             need.add((n.value[0], n.value[1]))
         elif n.op == "tabloc" and not TABLES[n.value].teven:
@@ -684,7 +717,7 @@ def emit_hip_functor(d: OdeDerivatives, struct_name: str) -> str:
     o.append(f"  static constexpr int XV = {d.xv}, UV = {d.uv}, PV = {d.pv}, NIN = {N};")
     o.append(f"  static constexpr int NNZ_J = {st['nnz_J']}, NNZ_H = {st['nnz_H_lower']};")
     o.append(f"  static constexpr int OPS_FJGH = {st['ops_fjgh']};   // operations of the value + J + g + H body (csrc/defect_resident.h: which looped form pays)")
-    nac = 1 + max([nd.value for nd in topo_order(_level_roots(d, 2)) if nd.op == "aconst"], default=-1)
+    nac = 1 + max([nd.value for nd in with_templates(_level_roots(d, 2)) if nd.op == "aconst"], default=-1)
     o.append(f"  static constexpr int NACONST = {nac};   // constants of the application the function reads (vf.ApplConst)")
     o.append(f"  static constexpr const char* name() {{ return \"{d.name}\"; }}")
     # structural sparsity: compact position of every J / H (packed lower) entry or -1, and its inverse.  The LGL workspace
@@ -899,7 +932,7 @@ def plan_units(d: OdeDerivatives, outs) -> List[list]:
             e += 1
 
     def cost(group):
-        return sum(1 for x in topo_order(lower_reciprocals([r for _, r in group])) if x.args)
+        return count_ops(lower_reciprocals([r for _, r in group]))
 
     cols = []
     for k in range(N):
@@ -917,8 +950,9 @@ def plan_units(d: OdeDerivatives, outs) -> List[list]:
 
 
 def saved_nodes(d: OdeDerivatives) -> List[Node]:
-    """Transcendental sub-expressions of the value function f (in schedule order)."""
-    return [nd for nd in topo_order(d.f) if nd.op in TRANSCENDENTAL]
+    """Transcendental sub-expressions of the value function f (in schedule order), and its roots: a solved equation is the most
+    expensive value a body can hold, and with it saved the derivative pass at the same point does not iterate again."""
+    return [nd for nd in topo_order(d.f) if nd.op in TRANSCENDENTAL or nd.op == "root"]
 
 
 def emit_c(d: OdeDerivatives, prefix: str) -> str:

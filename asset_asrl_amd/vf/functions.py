@@ -492,6 +492,39 @@ def ConstantScalar(irows: int, v: float) -> VectorFunction:
     return VectorFunction(irows, [G.const(v)])
 
 
+def ScalarRootFinder(fx: VectorFunction, *args) -> VectorFunction:
+    """``ScalarRootFinder(fx, iters, tol)`` / ``ScalarRootFinder(fx, dfx, iters, tol)``: the root ``s*`` of the scalar function
+    ``fx(s, p_1 .. p_k)`` in its FIRST input, by Newton's iteration from the value that input has at the call -- the reference's
+    ``vf.ScalarRootFinder`` (/root/reference/src/VectorFunctions/CommonFunctions/RootFinder.h:9-200).  The result is a scalar function
+    of the same ``fx.IRows()`` inputs ``[guess, p_1 .. p_k]`` and composes like any other: ``root.eval(stack(guess_expr, params...))``.
+
+    The iteration (:82-100): at most `iters` passes of ``F = fx(s, p)``; stop where ``|F| < tol``; else ``s -= F / D`` with
+    ``D = dfx(s, p)`` where a `dfx` is given and the symbolic ``dfx/ds`` otherwise.  There is no test after the last update, a root
+    that has not converged returns its last iterate, ``iters = 0`` returns the guess.  The derivatives are those of the implicit
+    function, ``ds*/dp_i = -F_pi / F_s`` at ``(s*, p)``, always from `fx` (:141-143, :179-190); the guess has none.  In a compiled
+    body the iteration is one bounded loop per distinct root (vf/codegen.py), shared by the value and every derivative."""
+    from .ir import RootTemplate
+    if len(args) == 2:
+        dfx, (iters, tol) = None, args
+    elif len(args) == 3:
+        dfx, iters, tol = args
+    else:
+        raise TypeError("ScalarRootFinder(fx, iters, tol) or ScalarRootFinder(fx, dfx, iters, tol)")
+    if not isinstance(fx, VectorFunction) or fx.ORows() != 1:
+        raise ValueError("ScalarRootFinder: fx is not a scalar function (one output)")
+    if dfx is not None:
+        if not isinstance(dfx, VectorFunction) or dfx.ORows() != 1:
+            raise ValueError("ScalarRootFinder: dfx is not a scalar function (one output)")
+        if dfx.IRows() != fx.IRows():
+            raise ValueError(f"ScalarRootFinder: dfx has {dfx.IRows()} inputs (IRows), fx has {fx.IRows()}")
+    if not _is_num(iters) or int(iters) != iters or iters < 0:
+        raise ValueError(f"ScalarRootFinder: iters = {iters!r} is not a non-negative integer")
+    if not _is_num(tol) or not np.isfinite(tol) or tol <= 0:
+        raise ValueError(f"ScalarRootFinder: tol = {tol!r} is not a finite positive number")
+    digest = RootTemplate.register(fx.outs[0], None if dfx is None else dfx.outs[0], fx.IRows(), int(iters), float(tol))
+    return VectorFunction(fx.IRows(), [G.root(digest, [G.var(i) for i in range(fx.IRows())])])
+
+
 class InterpTable1D:
     """Tabulated data ``v(t)`` interpolated along one axis, cubic (Hermite, nodal slopes from five-point differences) or linear,
     usable as a number-in / number-out interpolant on the host and as a node of an ODE or function expression -- the reference's

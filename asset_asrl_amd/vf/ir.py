@@ -40,6 +40,13 @@ TABLES: Dict[str, object] = {}      # digest -> table (anything with .ts, .vs, .
 # what "tabloc" and a "tabget" of the array 't' need) and one for the DATA, whose arrays are named: ``.arrays[name] = (numbers, row
 # length)``.  The argument of a "tabget" on the data is a flat index built from the axes' "tabloc" nodes -- sums and multiples of
 # piecewise-constant nodes, so piecewise constant, with no derivative, under the rules of this file.
+# An equation solved for one unknown (the reference's ScalarRootFinder, CommonFunctions/RootFinder.h): "root" = the number s* the
+# Newton iteration on a residual TEMPLATE F(s, p_1 .. p_k) reaches from its first argument, the guess; the other arguments are the
+# parameters.  The node's value is the digest of its template (residual, optional step derivative, iters, tol: RootTemplate below).
+# Like a table node it is opaque in value and has rules for the rest: ds*/dp_i = -F_pi / F_s at (s*, p), the partials of the template
+# taken symbolically and substituted -- ordinary expressions of this file that hold the node itself, so second derivatives are the
+# same rules applied again.  The guess has no derivative.
+ROOTS: Dict[str, "RootTemplate"] = {}    # digest -> template: registered by functions.ScalarRootFinder
 
 
 class Node:
@@ -73,6 +80,7 @@ class Graph:
     def __init__(self):
         self._table: Dict[tuple, Node] = {}
         self._dcache: Dict[Tuple[int, int], Node] = {}
+        self._rcache: Dict[Tuple[int, int], Node] = {}      # (root node id, argument) -> root_slope
         self.zero = self.const(0.0)
         self.one = self.const(1.0)
 
@@ -271,6 +279,25 @@ class Graph:
             return self.const(float(_tab_entry(TABLES[digest], arr, row, int(loc.value) + off)))
         return self._mk("tabget", (loc,), (digest, arr, int(row), int(off)))
 
+    def root(self, digest: str, args: Sequence[Node]) -> Node:
+        """The root of template `digest` from the guess ``args[0]`` with the parameters ``args[1:]``."""
+        if len(args) != ROOTS[digest].nin:
+            raise ValueError(f"root: the template has {ROOTS[digest].nin} inputs, {len(args)} arguments given")
+        return self._mk("root", tuple(args), digest)
+
+    def root_slope(self, n: Node, i: int) -> Node:
+        """d n / d (argument i) of a root node, i >= 1: ``-F_pi / F_s`` at (n, parameters) -- the implicit-function rule on the
+        residual (RootFinder.h:141-143), never on a given step derivative.  Holds n itself."""
+        rc = self._rcache
+        r = rc.get((n.id, i))
+        if r is None:
+            tpl = ROOTS[n.value]
+            vmap = {0: n}
+            vmap.update({j: a for j, a in enumerate(n.args) if j > 0})
+            Fp, Fs = self.substitute([tpl.partial(i), tpl.partial(0)], vmap)
+            r = rc[(n.id, i)] = self.neg(self.div(Fp, Fs))
+        return r
+
     # ---- n-ary helpers -------------------------------------------------------------
     def sum(self, xs: Iterable[Node]) -> Node:
         acc = self.zero
@@ -304,6 +331,13 @@ class Graph:
             return self.zero
         if op == "select":                     # the derivative of the branch the test picks (Conditional.h:215-250); the test itself has none
             return self.select(n.args[0], self.d(n.args[1], w), self.d(n.args[2], w))
+        if op == "root":                       # -sum_i (F_pi / F_s) dp_i/dw; the guess (argument 0) has no derivative
+            acc = self.zero
+            for i in range(1, len(n.args)):
+                dp = self.d(n.args[i], w)
+                if dp is not self.zero:
+                    acc = self.add(acc, self.mul(self.root_slope(n, i), dp))
+            return acc
         a = n.args[0]
         da = self.d(a, w)
         if op in _UNARY or op in ("powi", "powr"):
@@ -396,6 +430,11 @@ class Graph:
                 for w, x, y in zip(wrts, ga, gb):
                     self._acc(adj, w, self.select(c, x, y))
                 continue
+            if op == "root":                   # argument i receives bar (-F_pi / F_s); the guess receives nothing
+                for i in range(1, len(n.args)):
+                    if not n.args[i].is_const():
+                        self._acc(adj, n.args[i], self.mul(bar, self.root_slope(n, i)))
+                continue
             if op in _UNARY or op in ("powi", "powr"):
                 a = n.args[0]
                 self._acc(adj, a, self.mul(bar, self._dunary(n, a)))
@@ -485,6 +524,8 @@ class Graph:
             return self.tabloc(n.value, args[0])
         if op == "tabget":
             return self.tabget(*n.value, args[0])
+        if op == "root":
+            return self.root(n.value, args)
         if op == "add":
             return self.add(*args)
         if op == "sub":
@@ -500,6 +541,93 @@ class Graph:
         if op == "powr":
             return self.powr(args[0], n.value)
         return self.unary(op, args[0])
+
+
+class RootTemplate:
+    """What a "root" node iterates on: the residual ``F`` over the leaves var 0 (the iterate) and var 1..k (the parameters), the
+    expression ``D`` the Newton step divides by (a given one, or dF/ds), ``iters`` and ``tol``.  Registered under a digest of its
+    CONTENT (the structural keys of F and of a given D, the sizes, iters, tol), so the node's structural key, the emitted text and
+    the module cache key do not depend on what else the process built."""
+
+    @staticmethod
+    def register(F: Node, D_given, nin: int, iters: int, tol: float) -> str:
+        """The digest of the template of these parts, registered in ROOTS; an equation seen before is not built again."""
+        F, = GRAPH.strip_cuts([F])
+        if D_given is not None:
+            D_given, = GRAPH.strip_cuts([D_given])
+        key = f"root|{F.skey}|{D_given.skey if D_given is not None else '-'}|{int(nin)}|{int(iters)}|{float(tol)!r}"
+        digest = hashlib.blake2b(key.encode(), digest_size=8).hexdigest()
+        if digest not in ROOTS:
+            for e in (F, D_given):
+                if e is not None and any(x.op == "root" for x in topo_order([e])):
+                    raise ValueError("ScalarRootFinder: the template of a root holds another root (nested root templates are not "
+                                     "supported; a root may be a PARAMETER of another: root.eval(stack(guess, other_root, ...)))")
+            ROOTS[digest] = RootTemplate(F, D_given, nin, iters, tol, digest)
+        return digest
+
+    def __init__(self, F: Node, D_given, nin: int, iters: int, tol: float, digest: str):
+        self.F, self.nin, self.iters, self.tol, self.digest = F, int(nin), int(iters), float(tol), digest
+        self.given = D_given is not None
+        self._partials: Dict[int, Node] = {}
+        self.D = D_given if self.given else self.partial(0)
+
+    def partial(self, i: int) -> Node:
+        """dF / d(input i) of the template, symbolic."""
+        r = self._partials.get(i)
+        if r is None:
+            r = self._partials[i] = GRAPH.d(self.F, GRAPH.var(i))
+        return r
+
+    def nodes(self) -> List[Node]:
+        """What one pass of the loop evaluates."""
+        return topo_order([self.F, self.D])
+
+    def solve(self, guess: float, params: Sequence[float], aconst=()) -> float:
+        return self.iterate(guess, params, aconst)[0]
+
+    def iterate(self, guess: float, params: Sequence[float], aconst=()) -> Tuple[float, int]:
+        """The iteration in Python floats (RootFinder.h:82-100): at most `iters` passes, each ``F = fx(s, p)``, stop where
+        ``|F| < tol``, else ``s -= F / D``; no test after the last update.  Returns (s, the number of updates made)."""
+        s = float(guess)
+        y = [s] + [float(p) for p in params]
+        passes = 0
+        for _ in range(self.iters):
+            y[0] = s
+            F = evaluate([self.F], y, (), aconst)[0]
+            if abs(F) < self.tol:
+                break
+            passes += 1
+            D = evaluate([self.D], y, (), aconst)[0]
+            try:
+                s -= F / D
+            except ZeroDivisionError:          # (what the device gets from a zero step derivative)
+                s -= math.copysign(math.inf, F) * math.copysign(1.0, D) if F != 0.0 else math.nan
+        return s, passes
+
+
+def with_templates(roots: Sequence[Node]) -> List[Node]:
+    """topo_order(roots), and behind it the nodes of the templates of every root node in it (each template once): for the walkers
+    that ask what a body READS or COSTS -- table arrays, application constants -- and not how it is wired."""
+    order = topo_order(roots)
+    seen, extra = set(), []
+    for n in order:
+        if n.op == "root" and n.value not in seen:
+            seen.add(n.value)
+            extra += ROOTS[n.value].nodes()
+    return order + extra
+
+
+def count_ops(roots: Sequence[Node]) -> int:
+    """Operations of the expressions, shared nodes once.  A root counts as ``iters x (operations of its template + the test + the
+    divide + the update)``: an UPPER bound -- a lane leaves the loop at the trip its residual meets the tolerance."""
+    total = 0
+    for n in topo_order(roots):
+        if n.op == "root":
+            tpl = ROOTS[n.value]
+            total += tpl.iters * (sum(1 for x in tpl.nodes() if x.args) + 3)
+        elif n.args:
+            total += 1
+    return total
 
 
 def tab_array(tab, arr: str):
@@ -640,6 +768,8 @@ def _eval_node(n: Node, a: List[float], y, lam, aconst) -> float:
     if op == "tabget":
         dg, arr, row, off = n.value
         return float(_tab_entry(TABLES[dg], arr, row, int(a[0]) + off))
+    if op == "root":
+        return ROOTS[n.value].solve(a[0], a[1:], aconst)
     return _EVAL_UNARY[op](a[0])
 
 
